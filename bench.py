@@ -9,12 +9,19 @@ One "step" = one launch of the fused SPF+RouteDb kernel over the whole
 batch; one "build" = one (topology, source) SPF + RouteDb. Inputs are
 HBM-resident (torch-owned device buffers) before timing starts.
 
-The same JSON line carries sub-lines for C1 (single-source drop-in latency),
-C3 (fabric all-sources), C4 (link-failure sweep) and C5 (multi-area KSP2 +
-UCMP). Every config's output digest (openr_amd/csrc/host/route_digest.h,
-openr_amd/shard.py) is checked against the ORACLE's digest of the same
-workload (tests/golden/bench_digests.json, tests/golden/make_bench_digests.py):
-a mismatch prints the line and exits non-zero.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the
+headline figure needs and no more: it sets up the C3 fabric all-sources
+build, warms up, times the N steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints the JSON line.
+
+With --full the same JSON line carries sub-lines for C1 (single-source
+drop-in latency), C2 (topology batch), G1 (large WAN), C4 (link-failure
+sweep) and C5 (multi-area KSP2 + UCMP), the CPU baselines, the shard
+projection and the host-side f1-f4 figures, and every config's output digest
+(openr_amd/csrc/host/route_digest.h, openr_amd/shard.py) is checked against
+the ORACLE's digest of the same workload (tests/golden/bench_digests.json,
+tests/golden/make_bench_digests.py): a mismatch prints the line and exits
+non-zero.
 
 Multi-GPU (--gpus N via torch.distributed.run): each config shards its units
 over the ranks with no data-path collective; RCCL only all-gathers per-rank
@@ -128,6 +135,41 @@ def median(xs):
     xs = sorted(xs)
     n = len(xs)
     return xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together (limit 64 MB)
+DUMP_SEED = 0xD0
+
+
+def out_alloc(args):
+    """Output buffers of a timed path: zero-filled under --dump-outputs, so
+    that elements a kernel leaves unwritten compare equal between runs."""
+    return torch.zeros if args.dump_outputs else torch.empty
+
+
+def dump_outputs(args, arrays, rank, world):
+    """--dump-outputs DIR: the device arrays the last timed step left
+    (`arrays`: name -> 1-D tensor, exactly the elements a caller of the path
+    reads) as DIR/<name>.npy in float64 (exact for the 32-bit records). An
+    array past its share of DUMP_BUDGET_BYTES is written as a fixed sample:
+    its elements at sorted indices drawn from a generator seeded by
+    DUMP_SEED, the same for every run with the same arguments."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 8 // max(1, len(arrays) * world)
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        n = t.numel()
+        if n > cap:
+            idx = np.sort(rng.integers(0, n, size=cap, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        if world > 1:
+            name = f"{name}_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"),
+                t.cpu().numpy().astype(np.float64))
+    log(f"outputs of the last timed step written to {args.dump_outputs}")
 
 
 def oracle():
@@ -344,12 +386,14 @@ def finish_g1(out, digest, args):
 
 
 # ----------------------------------------------------------------- C3 ---
-def c3_launches(torch, M, capi, dev, names, ppn=100, with_sel=False, opts=None):
+def c3_launches(torch, M, capi, dev, names, ppn=100, with_sel=False, opts=None, alloc=None):
     """Host build + device upload of the C3 launches for the sources
     `names`: grouped by next-hop bitset width (SSW+RSW: 1 word, FSW: 3 words
     -> 4) so each launch writes masks of its own width. `opts`: another
-    fabric of the same naming (C3-ref, tests/test_gpu_bench_size.py)."""
+    fabric of the same naming (C3-ref, tests/test_gpu_bench_size.py).
+    `alloc`: the allocator of the output buffers (torch.empty by default)."""
     opts = dict(opts or C3_OPTS, prefixesPerNode=ppn)
+    alloc = alloc or torch.empty
     N = len(c3_source_names())
     launches = []
     fsw = [n for n in names if n.startswith("2-")]
@@ -369,11 +413,11 @@ def c3_launches(torch, M, capi, dev, names, ppn=100, with_sel=False, opts=None):
             ("edge_src", "int32"))}
         U = len(h["units"]) // 2
         Sn, Sp, W = h["max_nodes"], h["max_prefixes"], h["nh_words"]
-        o = dict(dist=torch.empty(U * Sn, dtype=torch.int32, device=dev),
-                 nh=torch.empty(U * W * Sn, dtype=torch.int32, device=dev),
-                 meta=torch.empty(U * Sp, dtype=torch.int32, device=dev),
-                 metric=torch.empty(U * Sp, dtype=torch.int32, device=dev),
-                 mask=torch.empty(U * W * Sp, dtype=torch.int32, device=dev))
+        o = dict(dist=alloc(U * Sn, dtype=torch.int32, device=dev),
+                 nh=alloc(U * W * Sn, dtype=torch.int32, device=dev),
+                 meta=alloc(U * Sp, dtype=torch.int32, device=dev),
+                 metric=alloc(U * Sp, dtype=torch.int32, device=dev),
+                 mask=alloc(U * W * Sp, dtype=torch.int32, device=dev))
         if with_sel:
             o["sel"] = torch.empty(U * Sp, dtype=torch.int32, device=dev)
         g = capi.Graph(h["num_topos"], Sn, h["max_edges"], h["max_degree"],
@@ -604,7 +648,7 @@ def run_c3(args, torch, dist, rank, world, local_rank):
         if not 0 <= shard_of[0] < shard_of[1]:
             raise SystemExit(f"bench.py: --as-rank {args.as_rank}: need 0 <= r < N")
     mine = shard.interleave(c3_source_names(), *shard_of)
-    launches, N = c3_launches(torch, M, capi, dev, mine, ppn)
+    launches, N = c3_launches(torch, M, capi, dev, mine, ppn, alloc=out_alloc(args))
     if args.c3_order == "wide-first":
         # the wide (FSW, 4-word) group has the longest units: dispatch it
         # first so it is not the lone tail after the 1-word group
@@ -634,11 +678,22 @@ def run_c3(args, torch, dist, rank, world, local_rank):
     kernel_ms = e0.elapsed_time(e1) / steps
     units = sum(L["U"] for L in launches)
     nbytes = sum(L["bytes"] for L in launches)
-    routes = sum(int(((L["o"]["meta"] & 1) != 0).sum().item()) for L in launches)
-    digest = shard.combine_digests(c3_digest(L) for L in launches)
+    # what a caller of the step reads: each width group's ogs_spf_out arrays
+    dump = {}
+    for L in launches:
+        o, Sn, Sp = L["o"], L["h"]["max_nodes"], L["h"]["max_prefixes"]
+        for k, n in (("dist", Sn), ("nh", L["W"] * Sn), ("meta", Sp), ("metric", Sp),
+                     ("mask", L["W"] * Sp)):
+            dump[f"c3_w{L['W']}_{k}"] = o[k][:L["U"] * n]
+    dump_outputs(args, dump, rank, world)
+    # the route count and the digest read every record back: --full only
+    routes = digest = 0
+    if args.full:
+        routes = sum(int(((L["o"]["meta"] & 1) != 0).sum().item()) for L in launches)
+        digest = shard.combine_digests(c3_digest(L) for L in launches)
     total_units, total_routes, _, tmax, _ = shard.reduce_stats(
         dist, torch, dev, units, routes, 0, wall)
-    job_digest = shard.reduce_xor(dist, torch, dev, [digest])[0]
+    job_digest = shard.reduce_xor(dist, torch, dev, [digest])[0] if args.full else None
     if rank != 0:
         return None
     achieved = nbytes / (kernel_ms * 1e-3) / 1e9
@@ -655,8 +710,6 @@ def run_c3(args, torch, dist, rank, world, local_rank):
                    "sources": N, "prefixes": N * ppn,
                    "parallelism": f"shard-by-source x{world}"},
         "route_dbs_per_s": round(total_units * steps / tmax, 1),
-        "routes_per_step": total_routes,
-        "route_digest": f"{job_digest:016x}",
         "gteps": round(43008 * total_units * steps / tmax / 1e9, 3),
         "kernel_ms": round(kernel_ms, 4),
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1),
@@ -664,7 +717,12 @@ def run_c3(args, torch, dist, rank, world, local_rank):
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
                      "bytes_alg_per_step_rank0": round(nbytes, 1)},
     }
-    log(f"c3 timed: {kernel_ms:.4f} ms/build, digest {job_digest:016x}")
+    if args.full:
+        line["routes_per_step"] = total_routes
+        line["route_digest"] = f"{job_digest:016x}"
+        log(f"c3 timed: {kernel_ms:.4f} ms/build, digest {job_digest:016x}")
+    else:
+        log(f"c3 timed: {kernel_ms:.4f} ms/build")
     if args.as_rank:
         r, n = shard_of
         line["metric"] = "SPF+RouteDb shard time (one rank's share, alone on one GPU)"
@@ -674,10 +732,12 @@ def run_c3(args, torch, dist, rank, world, local_rank):
         line["config"]["parallelism"] = f"rank {r} of {n} (interleaved sources), 1 GPU"
         line["config"]["sources"] = len(mine)
         line["shard_builds_per_s_projected"] = round(1e3 / kernel_ms, 2)
-        golden_check(line, f"c3_shard_{r}_of_{n}", job_digest,
-                     c3_golden_shard(mine) if ppn == 100 else None)
+        if args.full:
+            golden_check(line, f"c3_shard_{r}_of_{n}", job_digest,
+                         c3_golden_shard(mine) if ppn == 100 else None)
         return line
-    golden_check(line, "c3", job_digest, GOLDEN.get("c3") if ppn == 100 else None)
+    if args.full:
+        golden_check(line, "c3", job_digest, GOLDEN.get("c3") if ppn == 100 else None)
     if world == 1:
         set_traffic(line, "c3", ("spf_lds_route_kernel", "lds_prep_kernel"))
         if not args.no_shard_projection:
@@ -1404,8 +1464,30 @@ def main():
                          "(0: after RCCL's streams; A/B)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only join the process group and print the rank map (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the C1/C2/G1/C4/C5 "
+                         "sub-lines, CPU baselines, the shard projection, the host-side "
+                         "f1-f4 figures, output digests checked against the oracle's golden "
+                         "values and the perf floor. Off by default: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line. --config cN "
+                         "(one of those configs alone as the line) implies it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step of the headline "
+                         "(C3) path computed as DIR/<name>.npy (float64; a fixed seeded "
+                         "sample of each array, under 64 MB in all)")
     args = ap.parse_args()
     C3_GROUPS[0] = args.c3_launch == "groups"
+    if args.config != "all":
+        args.full = True
+    if args.dump_outputs and args.config not in ("all", "c3"):
+        ap.error("--dump-outputs writes the headline (C3) path's outputs: "
+                 "use it with --config all or c3")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1 timed step and --warmup 0 or more")
+    if not args.full:
+        # a plain run: the headline's set-up, warm-up and timed steps only
+        args.no_cpu_baseline = args.no_extras = args.no_shard_projection = True
+        args.no_c1 = args.no_g1 = args.no_c2 = args.no_c4 = args.no_c5 = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -1546,7 +1628,8 @@ def main():
         for k, v in ((line.get("g1_large_wan") or {}).get("single_source") or {}).get(
                 "golden", {}).items():
             line["golden"][k] = v
-        perf_summary(line)
+        if args.full:
+            perf_summary(line)
         finish(line)
     elif DIGEST_FAILURES:
         raise SystemExit(1)

@@ -15,6 +15,7 @@ the same LSDB; on the GPU the routes and the best-route selection must equal
 the oracle's and the fixture's bestKey / bestKeys."""
 import json
 import os
+import re
 
 import pytest
 
@@ -64,7 +65,14 @@ def test_reference_adj_bytes_decode(host_module, key):
     assert py["perfEvents"][0][2] > 1631213000000
 
 
-@pytest.mark.parametrize("key", sorted(k for k in KV if k.startswith("prefix:")))
+def _plain_id(key):
+    """A case id that can be selected as a node id: the key's "::", "/" and
+    brackets would end or split one ("prefix:n:area2:[fd00:4::/64]" ->
+    "prefix-n-area2-fd00-4-64")."""
+    return re.sub(r"[^A-Za-z0-9]+", "-", key).strip("-")
+
+
+@pytest.mark.parametrize("key", sorted(k for k in KV if k.startswith("prefix:")), ids=_plain_id)
 def test_reference_prefix_bytes_decode(host_module, key):
     py = tc.decode_prefix_db(KV[key])
     cc = host_module.decodePrefixDb(KV[key])

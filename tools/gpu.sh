@@ -8,7 +8,8 @@
 #   testfile:<path>           one test file
 #   smoke                     __graft_entry__.smoke()
 #   bench[:<args>]            python bench.py <args> (commas -> spaces)
-#   prof                      kernel trace + stats of the default bench (no cpu baseline)
+#   prof                      kernel trace + stats of `bench.py --full` (every sub-line, no
+#                             cpu baseline), left in $OGS_PROF_OUT (default prof_out/)
 #   pmc                       round PMC passes (tools/gpu_round_pmc.sh), OGS_COMMIT=<sha>
 #   c2scale[:<args>]          C2 kernel time vs batch size in one process (tools/c2_scaling.py)
 #   sq:<tag>:<bench args>     one SQ counter pass (wave-cycle split, LDS conflicts) over
@@ -31,6 +32,8 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 cd /tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 COMMIT=${OGS_COMMIT:-unknown}
+# where the `prof` recipe leaves its kernel trace (OGS_PROF_OUT=<dir> to move it)
+PROF_OUT=${OGS_PROF_OUT:-prof_out}
 
 step() {  # step <name> <timeout> <cmd...>
   local name=$1 t=$2; shift 2
@@ -64,8 +67,8 @@ for recipe in "$@"; do
     bench)
       step "bench_$n" 900 python bench.py ${rest//,/ } ;;
     prof)
-      step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o bench -- python3 bench.py --no-cpu-baseline --no-extras
-      grep -v "at::native" gpurun_out/prof/bench_kernel_stats.csv | cut -c1-200 | head -20 ;;
+      step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$PROF_OUT" -o bench -- python3 bench.py --full --no-cpu-baseline --no-extras
+      grep -v "at::native" "$PROF_OUT/bench_kernel_stats.csv" | cut -c1-200 | head -20 ;;
     pmc)
       OGS_COMMIT=$COMMIT step pmc 900 bash tools/gpu_round_pmc.sh ;;
     sq|sqlds)
