@@ -52,8 +52,9 @@ extern "C" {
  * statement ids, ogs_graph.rslot_ext (rows of 511+ edges). 4:
  * ogs_spf_routes_variants writes ogs_route_diff.base_desc_valid back. 5:
  * ogs_spf_routes_groups / ogs_route_group. 6: execution contexts
- * (ogs_ctx_create / ogs_ctx_set_option / ogs_ctx_* compute calls). */
-#define OGS_ABI_VERSION 6
+ * (ogs_ctx_create / ogs_ctx_set_option / ogs_ctx_* compute calls). 7: knob
+ * read-back (ogs_get_option / ogs_ctx_get_option / ogs_option_name). */
+#define OGS_ABI_VERSION 7
 
 /* ---- status codes ------------------------------------------------------ */
 #define OGS_OK 0
@@ -359,7 +360,8 @@ int ogs_host_free(void* hptr);
  *                 (sc1) loads; 0 agent-scope fences per round (A/B).
  *   "spf_global_lds": 1 (default) global-path distances and next-hop words
  *                 in LDS where both fit, else distances only; 2 distances
- *                 only; 0 all state in HBM (A/B).
+ *                 only; 3 distances and next-hop words in two phases, never
+ *                 the one-phase packed form; 0 all state in HBM (A/B).
  *   "ksp_hbm":    1 every KSP unit on the HBM-state path (A/B, tests); 0
  *                 (default) only units past LDS and OGS_F_EXACT_ORDER units.
  *                 "ksp_wave_trace": 1 (default) path traces of 32-bit
@@ -374,6 +376,11 @@ int ogs_host_free(void* hptr);
  *                 fixpoint. "ksp_stage": -1 (default) auto, 0 CSR read
  *                 from HBM/L2, 1 row offsets in LDS, 2 rows + edges in LDS. */
 int ogs_set_option(const char* name, int64_t value);
+/* Read-back (ABI 7): the knob's current value in the default context, and
+ * the knob names by index (0, 1, ...; NULL past the last one). A rejected
+ * ogs_set_option leaves the value as it was. */
+int ogs_get_option(const char* name, int64_t* value);
+const char* ogs_option_name(int32_t index);
 
 /* Smallest supported next-hop bitset width (words) for a source degree:
  * 1, 2, 4, 8 or 16 up to 512 links, ceil(degree / 32) past that (those
@@ -638,6 +645,7 @@ typedef struct ogs_ctx ogs_ctx;
 int ogs_ctx_create(int32_t device, ogs_ctx** out);
 int ogs_ctx_destroy(ogs_ctx* ctx); /* waits for the device, frees the scratch */
 int ogs_ctx_set_option(ogs_ctx* ctx, const char* name, int64_t value);
+int ogs_ctx_get_option(ogs_ctx* ctx, const char* name, int64_t* value); /* ABI 7 */
 int ogs_ctx_spf_routes(ogs_ctx* ctx, const ogs_graph* graph, const ogs_prefix_table* prefixes,
                        const ogs_unit* units, int32_t n_units, uint32_t flags,
                        int32_t nh_words, ogs_spf_out* out, void* stream);

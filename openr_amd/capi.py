@@ -1,12 +1,13 @@
 """ctypes view of the C-ABI (include/openr_gpu.h) — what a Python consumer of
 the boundary binds. bench.py drives the kernel through it with torch-owned
 device memory and torch's current HIP stream."""
+import contextlib
 import ctypes
 
 from . import LIB_PATH
 
 OGS_OK = 0
-OGS_ABI_VERSION = 6  # include/openr_gpu.h
+OGS_ABI_VERSION = 7  # include/openr_gpu.h
 OGS_F_ENABLE_V4 = 0x01
 OGS_F_V4_OVER_V6 = 0x02
 OGS_F_BEST_ROUTE_SELECTION = 0x04
@@ -26,6 +27,7 @@ EXPORTS = [
     "ogs_ctx_spf_routes_groups", "ogs_ctx_routes_from_spf", "ogs_ctx_spf_routes_variants",
     "ogs_ctx_ksp_paths", "ogs_ctx_ksp2_paths", "ogs_ctx_routes_multiarea",
     "ogs_ctx_rib_policy_apply",
+    "ogs_get_option", "ogs_ctx_get_option", "ogs_option_name",
 ]
 
 
@@ -78,6 +80,10 @@ def load(path=None):
     lib.ogs_spf_routes_groups.restype = ctypes.c_int
     lib.ogs_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int64]
     lib.ogs_set_option.restype = ctypes.c_int
+    lib.ogs_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
+    lib.ogs_get_option.restype = ctypes.c_int
+    lib.ogs_option_name.argtypes = [ctypes.c_int32]
+    lib.ogs_option_name.restype = ctypes.c_char_p
     # execution contexts (ABI 6): opaque handles
     lib.ogs_ctx_create.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
     lib.ogs_ctx_create.restype = ctypes.c_int
@@ -85,6 +91,9 @@ def load(path=None):
     lib.ogs_ctx_destroy.restype = ctypes.c_int
     lib.ogs_ctx_set_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]
     lib.ogs_ctx_set_option.restype = ctypes.c_int
+    lib.ogs_ctx_get_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p,
+                                       ctypes.POINTER(ctypes.c_int64)]
+    lib.ogs_ctx_get_option.restype = ctypes.c_int
     lib.ogs_ctx_spf_routes.argtypes = [ctypes.c_void_p] + lib.ogs_spf_routes.argtypes
     lib.ogs_ctx_spf_routes.restype = ctypes.c_int
     lib.ogs_ctx_spf_routes_groups.argtypes = ([ctypes.c_void_p] +
@@ -114,3 +123,29 @@ def load(path=None):
 def check(lib, rc, what):
     if rc != OGS_OK:
         raise RuntimeError(f"{what} failed ({rc}): {lib.ogs_last_error().decode()}")
+
+
+def get_option(lib, name):
+    """Current value of one default-context knob."""
+    value = ctypes.c_int64()
+    check(lib, lib.ogs_get_option(name.encode(), ctypes.byref(value)), name)
+    return value.value
+
+
+@contextlib.contextmanager
+def scoped_options(lib=None, **options):
+    """Set default-context knobs for one `with` block: each knob's current
+    value is read and the new one set (a rejected value raises through
+    check()); on exit, exceptions and a rejected later knob included, the
+    saved values go back in reverse order. Scopes nest."""
+    lib = lib or load()
+    saved = []
+    try:
+        for name, value in options.items():
+            old = get_option(lib, name)
+            check(lib, lib.ogs_set_option(name.encode(), value), name)
+            saved.append((name, old))
+        yield lib
+    finally:
+        for name, old in reversed(saved):
+            lib.ogs_set_option(name.encode(), old)

@@ -268,6 +268,32 @@ struct FlatTopology {
     return rslotExt.empty() ? nullptr : dRslotExt.as<uint32_t>();
   }
   DeviceBuffer dPatchIdx, dPatchVal;  // ogs_csr_patch staging (§8(f) f3)
+  // C-ABI descriptor of the device copy. The kernel dispatcher keys on which
+  // optional pointers are set, so graph() leaves all of them NULL (one
+  // topology, the maxima and the CSR arrays only), graphWithSlots() adds
+  // the slot arrays + edge_src, and a call site adds only what its call
+  // needs on top (topo_desc, rslot_ext).
+  ogs_graph graph() const {
+    ogs_graph g{};
+    g.num_topos = 1;
+    g.max_nodes = int32_t(names.size());
+    g.max_edges = int32_t(edges.size());
+    g.max_degree = maxDegree;
+    g.node_base = dNodeBase.as<uint32_t>();
+    g.row_ptr = dRow.as<uint32_t>();
+    g.edges = dEdges.as<uint64_t>();
+    g.node_flags = dFlags.as<uint8_t>();
+    return g;
+  }
+  ogs_graph graphWithSlots() const {
+    ogs_graph g = graph();
+    g.slot_node = slotStride ? dSlot.as<uint16_t>() : nullptr;
+    g.slot_stride = slotStride;
+    g.slot_edges = slotDegree ? dSlotEdges.as<uint32_t>() : nullptr;
+    g.slot_degree = slotDegree;
+    g.edge_src = dEdgeSrc.as<uint32_t>();
+    return g;
+  }
 };
 
 // ------------------------------------------------------------- LinkState --
@@ -929,6 +955,58 @@ struct HostBatch {
                 int* degreeOut = nullptr) const;
 };
 
+// Device copy of a HostBatch: its twelve arrays and the C-ABI descriptors
+// over them. graph() / table() fill what every user passes; the slot arrays
+// and rslot_ext stay NULL (the kernel dispatcher keys on them: a user with a
+// slot image adds it on top). Buffers are grow-only, so one image can be
+// uploaded again for the next batch.
+struct HostBatchImage {
+  DeviceBuffer nodeBase, desc, row, edges, edgeSrc, nodeFlags;            // graph
+  DeviceBuffer pfxBase, advOff, advNode, advMetrics, advMinNh, pfxFlags;  // table
+  void uploadGraph(const HostBatch& hb, void* stream = nullptr) {
+    nodeBase.upload(hb.nodeBase.data(), hb.nodeBase.size(), stream);
+    desc.upload(hb.topoDesc.data(), hb.topoDesc.size(), stream);
+    row.upload(hb.rowPtr.data(), hb.rowPtr.size(), stream);
+    edges.upload(hb.edges.data(), hb.edges.size(), stream);
+    edgeSrc.upload(hb.edgeSrc.data(), hb.edgeSrc.size(), stream);
+    nodeFlags.upload(hb.nodeFlags.data(), hb.nodeFlags.size(), stream);
+  }
+  void uploadTable(const HostBatch& hb, void* stream = nullptr) {
+    pfxBase.upload(hb.pfxBase.data(), hb.pfxBase.size(), stream);
+    advOff.upload(hb.advOff.data(), hb.advOff.size(), stream);
+    advNode.upload(hb.advNode.data(), hb.advNode.size(), stream);
+    advMetrics.upload(hb.advMetrics.data(), hb.advMetrics.size(), stream);
+    advMinNh.upload(hb.advMinNh.data(), hb.advMinNh.size(), stream);
+    pfxFlags.upload(hb.pfxFlags.data(), hb.pfxFlags.size(), stream);
+  }
+  ogs_graph graph(const HostBatch& hb, int numTopos) const {
+    ogs_graph g{};
+    g.num_topos = numTopos;
+    g.max_nodes = hb.maxNodes;
+    g.max_edges = hb.maxEdges;
+    g.max_degree = hb.maxDegree;
+    g.topo_desc = desc.as<uint32_t>();
+    g.node_base = nodeBase.as<uint32_t>();
+    g.row_ptr = row.as<uint32_t>();
+    g.edges = edges.as<uint64_t>();
+    g.node_flags = nodeFlags.as<uint8_t>();
+    g.edge_src = edgeSrc.as<uint32_t>();
+    return g;
+  }
+  ogs_prefix_table table(const HostBatch& hb) const {
+    ogs_prefix_table pt{};
+    pt.max_prefixes = hb.maxPrefixes;
+    pt.max_advertisements = hb.maxAdvs;
+    pt.pfx_base = pfxBase.as<uint32_t>();
+    pt.adv_off = advOff.as<uint32_t>();
+    pt.adv_node = advNode.as<uint32_t>();
+    pt.adv_metrics = advMetrics.as<int32_t>();
+    pt.adv_min_nh = advMinNh.as<int64_t>();
+    pt.pfx_flags = pfxFlags.as<uint8_t>();
+    return pt;
+  }
+};
+
 // ---------------------------------------------------- materialisation --
 // One unit's compact GPU results (host copies, distances widened to 64-bit,
 // all-ones = unreachable) and the host side of the prefix table.
@@ -1104,8 +1182,6 @@ class LinkFailureSweep {
  private:
   static constexpr int kDeadMax = 4;  // <= 2 links x 2 directions
   static constexpr size_t kDescMaxNodes = 16384;  // ogs_route_diff.base_desc bound
-  ogs_graph graph() const;
-  ogs_prefix_table table() const;
   void exactLaunch(void* stream);
   void exactFetch(void* stream);
   const LinkState& ls_;
@@ -1121,9 +1197,8 @@ class LinkFailureSweep {
   DeviceBuffer bDesc_;
   Mode mode_{kRepair};
   std::vector<uint32_t> dead_;
-  DeviceBuffer dNodeBase_, dDesc_, dRow_, dEdges_, dEdgeSrc_, dFlags_, dPfxBase_,
-      dAdvOff_, dAdvNode_, dAdvMetrics_, dAdvMinNh_, dPfxFlags_, dUnits_,
-      dBaseUnit_, dDead_, dAdvClass_;
+  HostBatchImage img_;  // device copy of hb_
+  DeviceBuffer dUnits_, dBaseUnit_, dDead_, dAdvClass_;
   DeviceBuffer bDist_, bNh_, bMeta_, bMetric_, bMask_, bSel_;
   DeviceBuffer dDist_, dNh_, dMeta_, dMetric_, dMask_, dSel_, dChanged_, dCounts_;
   DeviceBuffer dOffsets_, cPrefix_, cMeta_, cMetric_, cMask_;
@@ -1184,7 +1259,6 @@ class RouteDbBatch {
     DeviceBuffer units, dist, nh, meta, metric, mask, sel, reach;
   };
   ogs_graph graph() const;
-  ogs_prefix_table table() const;
   const SpfSolver& solver_;
   const LinkState* ls_{nullptr};
   std::string area_;
@@ -1195,8 +1269,7 @@ class RouteDbBatch {
   std::map<std::string, size_t> index_;
   std::vector<std::pair<size_t, size_t>> units_;  // source -> (group, unit)
   std::vector<Group> groups_;
-  DeviceBuffer dDesc_, dPfxBase_, dAdvOff_, dAdvNode_, dAdvMetrics_, dAdvMinNh_,
-      dPfxFlags_;
+  HostBatchImage img_;  // of hb_: the prefix table and the descriptor row only
   bool launched_{false};
   // multi-area domain: served node by node through a private solver's
   // multi-area buildRouteDb (areaLinkStates / prefixState must outlive it)

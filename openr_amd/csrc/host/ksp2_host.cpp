@@ -58,15 +58,7 @@ const std::vector<LinkState::Path>& LinkState::getKthPaths(
   dCount.resize(4);
   dLen.resize(maxPaths * 4);
   dEdges.resize(maxEdges * 4);
-  ogs_graph g{};
-  g.num_topos = 1;
-  g.max_nodes = int32_t(f.names.size());
-  g.max_edges = int32_t(E);
-  g.max_degree = f.maxDegree;
-  g.node_base = f.dNodeBase.as<uint32_t>();
-  g.row_ptr = f.dRow.as<uint32_t>();
-  g.edges = f.dEdges.as<uint64_t>();
-  g.node_flags = f.dFlags.as<uint8_t>();
+  ogs_graph g = f.graph();
   g.rslot_ext = f.rslotExtDev();  // rows of 512+ edges
   ogs_path_out out{dCount.as<uint32_t>(), dLen.as<uint32_t>(),
                    dEdges.as<uint32_t>(), maxPaths, maxEdges};
@@ -181,18 +173,15 @@ void Ksp2Batch::init(const std::string& src,
     dLen_[k].resize(nUnits_ * maxPaths_ * 4);
     dEdges2_[k].resize(nUnits_ * maxEdges_ * 4);
   }
+  if (T == 1) {  // the LinkState's own device CSR
+    g_ = fl[0]->graph();
+    g_.rslot_ext = fl[0]->rslotExtDev();
+    return;
+  }
   g_.num_topos = int32_t(T);
   g_.max_nodes = int32_t(maxN);
   g_.max_edges = int32_t(maxE);
   g_.max_degree = maxDeg;
-  if (T == 1) {  // the LinkState's own device CSR
-    g_.node_base = fl[0]->dNodeBase.as<uint32_t>();
-    g_.row_ptr = fl[0]->dRow.as<uint32_t>();
-    g_.edges = fl[0]->dEdges.as<uint64_t>();
-    g_.node_flags = fl[0]->dFlags.as<uint8_t>();
-    g_.rslot_ext = fl[0]->rslotExtDev();
-    return;
-  }
   // concatenated batch: global row offsets, topology-local edge targets
   std::vector<uint32_t> nodeBase{0}, row;
   std::vector<uint64_t> edges;

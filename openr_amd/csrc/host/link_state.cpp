@@ -608,20 +608,7 @@ const LinkState::SpfResult& LinkState::getSpfResult(const std::string& node,
     const ogs_unit u{0, s};
     sc.unit.upload(&u, 1);
     DeviceSpf& slot = newDeviceSpf(s, useLinkMetric, N, W, db, exact);
-    ogs_graph g{};
-    g.num_topos = 1;
-    g.max_nodes = int32_t(N);
-    g.max_edges = int32_t(f.edges.size());
-    g.max_degree = f.maxDegree;
-    g.node_base = f.dNodeBase.as<uint32_t>();
-    g.row_ptr = f.dRow.as<uint32_t>();
-    g.edges = f.dEdges.as<uint64_t>();
-    g.node_flags = f.dFlags.as<uint8_t>();
-    g.slot_node = f.slotStride ? f.dSlot.as<uint16_t>() : nullptr;
-    g.slot_stride = f.slotStride;
-    g.slot_edges = f.slotDegree ? f.dSlotEdges.as<uint32_t>() : nullptr;
-    g.slot_degree = f.slotDegree;
-    g.edge_src = f.dEdgeSrc.as<uint32_t>();
+    const ogs_graph g = f.graphWithSlots();
     ogs_spf_out out{};
     out.dist = slot.dist();
     out.nh = slot.nh();

@@ -81,13 +81,10 @@ RouteDbBatch::RouteDbBatch(const SpfSolver& solver, const AreaLinkStates& als,
     units_[i] = {size_t(g - groups_.begin()), g->members.size()};
     g->members.push_back(uint32_t(i));
   }
-  dDesc_.upload(hb_.topoDesc.data(), hb_.topoDesc.size());
-  dPfxBase_.upload(hb_.pfxBase.data(), hb_.pfxBase.size());
-  dAdvOff_.upload(hb_.advOff.data(), hb_.advOff.size());
-  dAdvNode_.upload(hb_.advNode.data(), hb_.advNode.size());
-  dAdvMetrics_.upload(hb_.advMetrics.data(), hb_.advMetrics.size());
-  dAdvMinNh_.upload(hb_.advMinNh.data(), hb_.advMinNh.size());
-  dPfxFlags_.upload(hb_.pfxFlags.data(), hb_.pfxFlags.size());
+  // the CSR is the LinkState's own device copy (graph()): of hb_ only the
+  // descriptor row and the prefix table go up
+  img_.desc.upload(hb_.topoDesc.data(), hb_.topoDesc.size());
+  img_.uploadTable(hb_);
   const size_t Sn = size_t(std::max(hb_.maxNodes, 1)), Sp = size_t(std::max(hb_.maxPrefixes, 1));
   const size_t db = wide_ ? 8 : 4;
   for (Group& g : groups_) {
@@ -106,36 +103,9 @@ RouteDbBatch::RouteDbBatch(const SpfSolver& solver, const AreaLinkStates& als,
 }
 
 ogs_graph RouteDbBatch::graph() const {
-  const FlatTopology& f = ls_->flatOnDevice();
-  ogs_graph g{};
-  g.num_topos = 1;
-  g.max_nodes = int32_t(f.names.size());
-  g.max_edges = int32_t(f.edges.size());
-  g.max_degree = f.maxDegree;
-  g.topo_desc = dDesc_.as<uint32_t>();
-  g.node_base = f.dNodeBase.as<uint32_t>();
-  g.row_ptr = f.dRow.as<uint32_t>();
-  g.edges = f.dEdges.as<uint64_t>();
-  g.node_flags = f.dFlags.as<uint8_t>();
-  g.slot_node = f.slotStride ? f.dSlot.as<uint16_t>() : nullptr;
-  g.slot_stride = f.slotStride;
-  g.slot_edges = f.slotDegree ? f.dSlotEdges.as<uint32_t>() : nullptr;
-  g.slot_degree = f.slotDegree;
-  g.edge_src = f.dEdgeSrc.as<uint32_t>();
+  ogs_graph g = ls_->flatOnDevice().graphWithSlots();
+  g.topo_desc = img_.desc.as<uint32_t>();
   return g;
-}
-
-ogs_prefix_table RouteDbBatch::table() const {
-  ogs_prefix_table pt{};
-  pt.max_prefixes = hb_.maxPrefixes;
-  pt.max_advertisements = hb_.maxAdvs;
-  pt.pfx_base = dPfxBase_.as<uint32_t>();
-  pt.adv_off = dAdvOff_.as<uint32_t>();
-  pt.adv_node = dAdvNode_.as<uint32_t>();
-  pt.adv_metrics = dAdvMetrics_.as<int32_t>();
-  pt.adv_min_nh = dAdvMinNh_.as<int64_t>();
-  pt.pfx_flags = dPfxFlags_.as<uint8_t>();
-  return pt;
 }
 
 void RouteDbBatch::launch(void* stream) {
@@ -144,7 +114,7 @@ void RouteDbBatch::launch(void* stream) {
     return;
   }
   const ogs_graph g = graph();
-  const ogs_prefix_table pt = table();
+  const ogs_prefix_table pt = img_.table(hb_);
   const uint32_t flags = (solver_.enableV4_ ? OGS_F_ENABLE_V4 : 0u) |
       (solver_.v4OverV6Nexthop_ ? OGS_F_V4_OVER_V6 : 0u) |
       (solver_.enableBestRouteSelection_ ? OGS_F_BEST_ROUTE_SELECTION : 0u) |

@@ -86,18 +86,8 @@ LinkFailureSweep::LinkFailureSweep(
   words_ = (Sp_ + 31) / 32;
   std::vector<ogs_unit> units(U, ogs_unit{0, s});
   const ogs_unit base{0, s};
-  dNodeBase_.upload(hb_.nodeBase.data(), hb_.nodeBase.size());
-  dDesc_.upload(hb_.topoDesc.data(), hb_.topoDesc.size());
-  dRow_.upload(hb_.rowPtr.data(), hb_.rowPtr.size());
-  dEdges_.upload(hb_.edges.data(), hb_.edges.size());
-  dEdgeSrc_.upload(hb_.edgeSrc.data(), hb_.edgeSrc.size());
-  dFlags_.upload(hb_.nodeFlags.data(), hb_.nodeFlags.size());
-  dPfxBase_.upload(hb_.pfxBase.data(), hb_.pfxBase.size());
-  dAdvOff_.upload(hb_.advOff.data(), hb_.advOff.size());
-  dAdvNode_.upload(hb_.advNode.data(), hb_.advNode.size());
-  dAdvMetrics_.upload(hb_.advMetrics.data(), hb_.advMetrics.size());
-  dAdvMinNh_.upload(hb_.advMinNh.data(), hb_.advMinNh.size());
-  dPfxFlags_.upload(hb_.pfxFlags.data(), hb_.pfxFlags.size());
+  img_.uploadGraph(hb_);
+  img_.uploadTable(hb_);
   dUnits_.upload(units.data(), units.size());
   dBaseUnit_.upload(&base, 1);
   dDead_.upload(dead_.data(), dead_.size());
@@ -162,8 +152,8 @@ void LinkFailureSweep::exactLaunch(void* stream) {
   xMeta_.assign(T * Sp_, 0);
   xMetric_.assign(T * Sp_, 0);
   xMask_.assign(T * W_ * Sp_, 0);
-  DeviceBuffer nodeBase, desc, row, edges, edgeSrc, nflags, pfxBase, advOff, advNode,
-      advMetrics, advMinNh, pfxFlags, units, meta, metric, mask;
+  HostBatchImage img;  // reused (grow-only) by every chunk
+  DeviceBuffer units, meta, metric, mask;
   for (size_t c0 = 0; c0 < T; c0 += kExactChunk) {
     const size_t c1 = std::min(T, c0 + kExactChunk), n = c1 - c0;
     HostBatch hb;  // topology t - c0 = the base (t = 0) or variant t - 1
@@ -178,42 +168,14 @@ void LinkFailureSweep::exactLaunch(void* stream) {
     }
     std::vector<ogs_unit> us(n);
     for (size_t i = 0; i < n; ++i) us[i] = ogs_unit{uint32_t(i), s};
-    nodeBase.upload(hb.nodeBase.data(), hb.nodeBase.size(), stream);
-    desc.upload(hb.topoDesc.data(), hb.topoDesc.size(), stream);
-    row.upload(hb.rowPtr.data(), hb.rowPtr.size(), stream);
-    edges.upload(hb.edges.data(), hb.edges.size(), stream);
-    edgeSrc.upload(hb.edgeSrc.data(), hb.edgeSrc.size(), stream);
-    nflags.upload(hb.nodeFlags.data(), hb.nodeFlags.size(), stream);
-    pfxBase.upload(hb.pfxBase.data(), hb.pfxBase.size(), stream);
-    advOff.upload(hb.advOff.data(), hb.advOff.size(), stream);
-    advNode.upload(hb.advNode.data(), hb.advNode.size(), stream);
-    advMetrics.upload(hb.advMetrics.data(), hb.advMetrics.size(), stream);
-    advMinNh.upload(hb.advMinNh.data(), hb.advMinNh.size(), stream);
-    pfxFlags.upload(hb.pfxFlags.data(), hb.pfxFlags.size(), stream);
+    img.uploadGraph(hb, stream);
+    img.uploadTable(hb, stream);
     units.upload(us.data(), us.size(), stream);
     meta.resize(n * Sp_ * 4);
     metric.resize(n * Sp_ * 8);
     mask.resize(n * W_ * Sp_ * 4);
-    ogs_graph g{};
-    g.num_topos = int32_t(n);
-    g.max_nodes = hb.maxNodes;
-    g.max_edges = hb.maxEdges;
-    g.max_degree = hb.maxDegree;
-    g.topo_desc = desc.as<uint32_t>();
-    g.node_base = nodeBase.as<uint32_t>();
-    g.row_ptr = row.as<uint32_t>();
-    g.edges = edges.as<uint64_t>();
-    g.node_flags = nflags.as<uint8_t>();
-    g.edge_src = edgeSrc.as<uint32_t>();
-    ogs_prefix_table pt{};
-    pt.max_prefixes = hb.maxPrefixes;
-    pt.max_advertisements = hb.maxAdvs;
-    pt.pfx_base = pfxBase.as<uint32_t>();
-    pt.adv_off = advOff.as<uint32_t>();
-    pt.adv_node = advNode.as<uint32_t>();
-    pt.adv_metrics = advMetrics.as<int32_t>();
-    pt.adv_min_nh = advMinNh.as<int64_t>();
-    pt.pfx_flags = pfxFlags.as<uint8_t>();
+    const ogs_graph g = img.graph(hb, int(n));
+    const ogs_prefix_table pt = img.table(hb);
     ogs_spf_out out{nullptr, nullptr, meta.as<uint32_t>(), metric.get(), mask.as<uint32_t>(),
                     nullptr};
     ogsCheck(ogs_spf_routes(&g, &pt, units.as<ogs_unit>(), int32_t(n), fl, W_, &out, stream),
@@ -263,38 +225,10 @@ uint32_t LinkFailureSweep::flags() const {
   return (enableV4_ ? OGS_F_ENABLE_V4 : 0u) | (brs_ ? OGS_F_BEST_ROUTE_SELECTION : 0u);
 }
 
-ogs_graph LinkFailureSweep::graph() const {
-  ogs_graph g{};
-  g.num_topos = 1;
-  g.max_nodes = hb_.maxNodes;
-  g.max_edges = hb_.maxEdges;
-  g.max_degree = hb_.maxDegree;
-  g.topo_desc = dDesc_.as<uint32_t>();
-  g.node_base = dNodeBase_.as<uint32_t>();
-  g.row_ptr = dRow_.as<uint32_t>();
-  g.edges = dEdges_.as<uint64_t>();
-  g.node_flags = dFlags_.as<uint8_t>();
-  g.edge_src = dEdgeSrc_.as<uint32_t>();
-  return g;
-}
-
-ogs_prefix_table LinkFailureSweep::table() const {
-  ogs_prefix_table pt{};
-  pt.max_prefixes = hb_.maxPrefixes;
-  pt.max_advertisements = hb_.maxAdvs;
-  pt.pfx_base = dPfxBase_.as<uint32_t>();
-  pt.adv_off = dAdvOff_.as<uint32_t>();
-  pt.adv_node = dAdvNode_.as<uint32_t>();
-  pt.adv_metrics = dAdvMetrics_.as<int32_t>();
-  pt.adv_min_nh = dAdvMinNh_.as<int64_t>();
-  pt.pfx_flags = dPfxFlags_.as<uint8_t>();
-  return pt;
-}
-
 void LinkFailureSweep::runBase(void* stream) {
   if (exact_) return exactLaunch(stream);
-  ogs_graph g = graph();
-  ogs_prefix_table pt = table();
+  const ogs_graph g = img_.graph(hb_, 1);
+  const ogs_prefix_table pt = img_.table(hb_);
   ogs_spf_out out{bDist_.get(), bNh_.as<uint32_t>(), bMeta_.as<uint32_t>(),
                   bMetric_.get(), bMask_.as<uint32_t>(), bSel_.as<uint32_t>()};
   ogsCheck(ogs_spf_routes(&g, &pt, dBaseUnit_.as<ogs_unit>(), 1, flags(), W_, &out, stream),
@@ -311,8 +245,8 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   changed_.clear();
   meta_.clear();
   counts_.clear();
-  ogs_graph g = graph();
-  ogs_prefix_table pt = table();
+  const ogs_graph g = img_.graph(hb_, 1);
+  const ogs_prefix_table pt = img_.table(hb_);
   const bool changedOnly = mode_ == kChangedOnly && W_ == 1;
   ogs_spf_out out{};
   if (records) {

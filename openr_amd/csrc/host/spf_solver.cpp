@@ -800,22 +800,9 @@ void addNodeLabelRoutes(const LinkState& ls, const FlatTopology& f,
 
 namespace {
 
-ogs_graph singleGraph(const FlatTopology& f, const uint32_t* desc) {
-  ogs_graph g{};
-  g.num_topos = 1;
-  g.max_nodes = int32_t(f.names.size());
-  g.max_edges = int32_t(f.edges.size());
-  g.max_degree = f.maxDegree;
+inline ogs_graph singleGraph(const FlatTopology& f, const uint32_t* desc) {
+  ogs_graph g = f.graphWithSlots();
   g.topo_desc = desc;
-  g.node_base = f.dNodeBase.as<uint32_t>();
-  g.row_ptr = f.dRow.as<uint32_t>();
-  g.edges = f.dEdges.as<uint64_t>();
-  g.node_flags = f.dFlags.as<uint8_t>();
-  g.slot_node = f.slotStride ? f.dSlot.as<uint16_t>() : nullptr;
-  g.slot_stride = f.slotStride;
-  g.slot_edges = f.slotDegree ? f.dSlotEdges.as<uint32_t>() : nullptr;
-  g.slot_degree = f.slotDegree;
-  g.edge_src = f.dEdgeSrc.as<uint32_t>();
   return g;
 }
 

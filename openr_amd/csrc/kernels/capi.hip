@@ -1,8 +1,10 @@
 // capi.hip — extern "C" entry points of libopenr_gpu.so (include/openr_gpu.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 
@@ -149,203 +151,65 @@ int ogs_stream_sync(void* stream) {
 
 }  // extern "C"
 
-// one knob of `o` (the default context's, or a context's own)
-static int set_option(ogs::EngineOptions& o, const char* name, int64_t value) {
-  if (!name) return fail(OGS_E_INVALID, "option name is NULL");
-  if (std::strcmp(name, "unit_width") == 0) {
-    if (value != -1 && value != 0 && value != 1 && value != 2 && value != 3 &&
-        value != 64 && value != 128 && value != 256) {
-      return fail(OGS_E_INVALID, "unit_width must be -1, 0, 1, 2, 3, 64, 128 or 256");
-    }
-    o.unitWidth = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ms_group") == 0) {
-    if (value != 0 && value != 1 && value != 2 && value != 4) {
-      return fail(OGS_E_INVALID, "ms_group must be 0, 1, 2 or 4");
-    }
-    o.msGroup = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "route_stream") == 0) {
-    if (value != 1 && value != 2 && value != 4 && value != 5) {
-      return fail(OGS_E_INVALID, "route_stream must be 1, 2, 4 or 5");
-    }
-    o.routeStream = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_parts") == 0) {
-    if (value < 0 || value > 64) return fail(OGS_E_INVALID, "lds_parts must be in [0, 64]");
-    o.ldsParts = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_tail") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "lds_tail must be 0 or 1");
-    o.ldsTail = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_lead") == 0) {
-    if (value < -1 || value > 65536) return fail(OGS_E_INVALID, "lds_lead must be in [-1, 65536]");
-    o.ldsLead = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_tail_parts") == 0) {
-    if (value < 0 || value > 64) return fail(OGS_E_INVALID, "lds_tail_parts must be in [0, 64]");
-    o.ldsTailParts = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_pull") == 0) {
-    if (value < 0 || value > 15) return fail(OGS_E_INVALID, "lds_pull must be in [0, 15]");
-    o.ldsPull = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_bfs_exit") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "lds_bfs_exit must be 0 or 1");
-    o.ldsBfsExit = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_key16") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "lds_key16 must be 0 or 1");
-    o.ldsKey16 = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "lds_grid") == 0) {
-    if (value < 0 || value > 4096) return fail(OGS_E_INVALID, "lds_grid must be in [0, 4096]");
-    o.ldsGrid = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_packed_scan") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "spf_packed_scan must be 0 or 1");
-    o.spfPackedScan = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "route_store_nt") == 0) {
-    if (value < 0 || value > 3) return fail(OGS_E_INVALID, "route_store_nt must be in [0, 3]");
-    o.routeStoreNt = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "frontier_block") == 0) {
-    if (value != 0 && value != 256 && value != 512 && value != 1024) {
-      return fail(OGS_E_INVALID, "frontier_block must be 0, 256, 512 or 1024");
-    }
-    o.frontierBlock = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "frontier_parts") == 0) {
-    if (value < 0 || value > 16) return fail(OGS_E_INVALID, "frontier_parts must be in [0, 16]");
-    o.frontierParts = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_lane_walk") == 0) {
-    if (value < -1 || value > 1) return fail(OGS_E_INVALID, "spf_lane_walk must be -1, 0 or 1");
-    o.spfLaneWalk = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_preload") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "spf_preload must be 0 or 1");
-    o.spfPreload = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "frontier_parts_wide") == 0) {
-    if (value < 0 || value > 16) {
-      return fail(OGS_E_INVALID, "frontier_parts_wide must be in [0, 16]");
-    }
-    o.frontierPartsWide = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_seed_row") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "spf_seed_row must be 0 or 1");
-    o.spfSeedRow = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_frontier") == 0) {
-    if (value != 0 && value != 1) {
-      return fail(OGS_E_INVALID, "spf_frontier must be 0 or 1");
-    }
-    o.spfFrontier = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_global") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "spf_global must be 0 or 1");
-    o.spfGlobal = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ksp_queue") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "ksp_queue must be 0 or 1");
-    o.kspQueue = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_global_sync") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "spf_global_sync must be 0 or 1");
-    o.spfGlobalSync = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_global_lds") == 0) {
-    if (value < 0 || value > 3) return fail(OGS_E_INVALID, "spf_global_lds must be 0..3");
-    o.spfGlobalLds = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "c4_desc") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "c4_desc must be 0 or 1");
-    o.c4Desc = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ksp_hbm") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "ksp_hbm must be 0 or 1");
-    o.kspHbm = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ksp_stage") == 0) {
-    if (value < -1 || value > 2) return fail(OGS_E_INVALID, "ksp_stage must be -1, 0, 1 or 2");
-    o.kspStage = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_ninfo") == 0) {
-    if (value < -1 || value > 1) return fail(OGS_E_INVALID, "spf_ninfo must be -1, 0 or 1");
-    o.spfNinfo = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "spf_queue") == 0) {
-    if (value != -1 && value != 0) return fail(OGS_E_INVALID, "spf_queue must be -1 or 0");
-    o.spfQueue = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "wave_upb") == 0) {
-    if (value != 4 && value != 8 && value != 16) {
-      return fail(OGS_E_INVALID, "wave_upb must be 4, 8 or 16");
-    }
-    o.waveUpb = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ksp_prune") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "ksp_prune must be 0 or 1");
-    o.kspPrune = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "ksp_wave_trace") == 0) {
-    if (value != 0 && value != 1) return fail(OGS_E_INVALID, "ksp_wave_trace must be 0 or 1");
-    o.kspWaveTrace = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "wave_opt") == 0) {
-    if (value < 0 || value > 3) return fail(OGS_E_INVALID, "wave_opt must be in [0, 3]");
-    o.waveOpt = int(value);
-    return OGS_OK;
-  }
-  if (std::strcmp(name, "wave_wg_lds") == 0) {
-    if (value < 0 || value > 160 * 1024) {
-      return fail(OGS_E_INVALID, "wave_wg_lds must be in [0, 163840]");
-    }
-    o.waveWgLds = int(value);
-    return OGS_OK;
-  }
-  return fail(OGS_E_INVALID, std::string("unknown option ") + name);
+// the ogs_set_option knobs, generated from OGS_ENGINE_OPTIONS (engine.h)
+namespace {
+struct OptionSpec {
+  const char* name;
+  int ogs::EngineOptions::*member;
+  bool (*accepts)(int64_t);  // on the caller's int64_t, before it narrows
+  const char* accepted;      // "in [lo, hi]" / "one of a, b, c"
+};
+bool in_list(int64_t v, std::initializer_list<int64_t> list) {
+  return std::find(list.begin(), list.end(), v) != list.end();
 }
+#define OGS_RANGE(lo, hi) v >= (lo) && v <= (hi), "in [" #lo ", " #hi "]"
+#define OGS_LIST(...) in_list(v, {__VA_ARGS__}), "one of " #__VA_ARGS__
+#define OGS_SPEC(name, member, test, text) {name, member, [](int64_t v) { return test; }, text},
+#define OGS_OPTION_SPEC(name, member, def, accepted) \
+  OGS_SPEC(#name, &ogs::EngineOptions::member, accepted)
+const OptionSpec kOptions[] = {OGS_ENGINE_OPTIONS(OGS_OPTION_SPEC)};
+constexpr int kNumOptions = int(sizeof(kOptions) / sizeof(kOptions[0]));
+
+const OptionSpec* find_option(const char* name) {
+  for (const OptionSpec& s : kOptions) {
+    if (std::strcmp(name, s.name) == 0) return &s;
+  }
+  return nullptr;
+}
+
+// one knob of `o` (the default context's, or a context's own)
+int set_option(ogs::EngineOptions& o, const char* name, int64_t value) {
+  if (!name) return fail(OGS_E_INVALID, "option name is NULL");
+  const OptionSpec* s = find_option(name);
+  if (!s) return fail(OGS_E_INVALID, std::string("unknown option ") + name);
+  if (!s->accepts(value)) {
+    return fail(OGS_E_INVALID, std::string(name) + " must be " + s->accepted);
+  }
+  o.*(s->member) = int(value);
+  return OGS_OK;
+}
+
+int get_option(const ogs::EngineOptions& o, const char* name, int64_t* value) {
+  if (!name || !value) return fail(OGS_E_INVALID, "option name or value is NULL");
+  const OptionSpec* s = find_option(name);
+  if (!s) return fail(OGS_E_INVALID, std::string("unknown option ") + name);
+  *value = o.*(s->member);
+  return OGS_OK;
+}
+}  // namespace
 
 extern "C" {
 
 int ogs_set_option(const char* name, int64_t value) {
   return set_option(ogs::default_options(), name, value);
+}
+
+int ogs_get_option(const char* name, int64_t* value) {
+  return get_option(ogs::default_options(), name, value);
+}
+
+const char* ogs_option_name(int32_t index) {
+  return index >= 0 && index < kNumOptions ? kOptions[index].name : nullptr;
 }
 
 // ---- contexts (ABI 6) ------------------------------------------------------
@@ -380,6 +244,11 @@ int ogs_ctx_set_option(ogs_ctx* ctx, const char* name, int64_t value) {
   return set_option(ctx->e.opts, name, value);
 }
 
+int ogs_ctx_get_option(ogs_ctx* ctx, const char* name, int64_t* value) {
+  if (!ctx) return fail(OGS_E_INVALID, "ctx is NULL");
+  return get_option(ctx->e.opts, name, value);
+}
+
 // any width from ceil(degree/32) up is valid for a call; this is the
 // smallest power-of-two width (the templated kernels) up to 16 words
 int ogs_nh_words_for_degree(int degree) {
@@ -391,16 +260,36 @@ int ogs_nh_words_for_degree(int degree) {
   return words;  // sources of more than 512 links: exact width
 }
 
+// The argument rules more than one entry point applies, stated once. Each
+// entry point keeps its own order of checks: OGS_E_UNSUPPORTED (max_nodes)
+// wins over the OGS_E_INVALID checks that come after it, not over the ones
+// before.
+static bool prefix_arrays_set(const ogs_prefix_table* p) {
+  return p->pfx_base && p->adv_off && p->adv_node && p->adv_metrics && p->adv_min_nh &&
+         p->pfx_flags;
+}
+
+static int check_max_nodes(const ogs_graph* graph) {
+  if (graph->max_nodes <= 0 || uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
+    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
+  }
+  return OGS_OK;
+}
+
+static int check_rslot_ext(const ogs_graph* graph) {
+  if (graph->max_degree >= OGS_MAX_DEGREE && !graph->rslot_ext) {
+    return fail(OGS_E_INVALID, "rows of 512+ edges need graph->rslot_ext");
+  }
+  return OGS_OK;
+}
+
 // Shape checks shared by ogs_spf_routes and ogs_spf_routes_groups.
 static int check_routes_args(const ogs_graph* graph, const ogs_prefix_table* prefixes,
                              uint32_t flags) {
   if (!graph->node_base || !graph->row_ptr || !graph->node_flags) {
     return fail(OGS_E_INVALID, "graph arrays are NULL");
   }
-  if (graph->max_nodes <= 0 ||
-      uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
-    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
-  }
+  if (int rc = check_max_nodes(graph)) return rc;
   if (graph->slot_node && graph->slot_stride != 64 &&
       graph->slot_stride != 128 && graph->slot_stride != 256) {
     return fail(OGS_E_INVALID, "slot_stride must be 64, 128 or 256");
@@ -412,9 +301,7 @@ static int check_routes_args(const ogs_graph* graph, const ogs_prefix_table* pre
       (!graph->slot_node || (graph->slot_degree != 4 && graph->slot_degree != 8))) {
     return fail(OGS_E_INVALID, "slot_edges needs slot_node and slot_degree 4 or 8");
   }
-  if (prefixes && (!prefixes->pfx_base || !prefixes->adv_off ||
-                   !prefixes->adv_node || !prefixes->adv_metrics ||
-                   !prefixes->adv_min_nh || !prefixes->pfx_flags)) {
+  if (prefixes && !prefix_arrays_set(prefixes)) {
     return fail(OGS_E_INVALID, "prefix table arrays are NULL");
   }
   if ((flags & OGS_F_EXACT_ORDER) && !(flags & OGS_F_WIDE_METRIC)) {
@@ -454,34 +341,10 @@ int ogs_spf_routes(const ogs_graph* graph, const ogs_prefix_table* prefixes,
   if (!graph || !out) return fail(OGS_E_INVALID, "graph/out is NULL");
   if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
   if (n_units == 0) return OGS_OK;
-  if (!units || !graph->node_base || !graph->row_ptr || !graph->node_flags) {
-    return fail(OGS_E_INVALID, "graph arrays are NULL");
-  }
-  if (graph->max_nodes <= 0 ||
-      uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
-    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
-  }
-  if (graph->slot_node && graph->slot_stride != 64 &&
-      graph->slot_stride != 128 && graph->slot_stride != 256) {
-    return fail(OGS_E_INVALID, "slot_stride must be 64, 128 or 256");
-  }
-  if (graph->slot_node && graph->slot_stride < graph->max_nodes) {
-    return fail(OGS_E_INVALID, "slot_stride < max_nodes");
-  }
-  if (graph->slot_edges &&
-      (!graph->slot_node || (graph->slot_degree != 4 && graph->slot_degree != 8))) {
-    return fail(OGS_E_INVALID, "slot_edges needs slot_node and slot_degree 4 or 8");
-  }
-  if (prefixes && (!prefixes->pfx_base || !prefixes->adv_off ||
-                   !prefixes->adv_node || !prefixes->adv_metrics ||
-                   !prefixes->adv_min_nh || !prefixes->pfx_flags)) {
-    return fail(OGS_E_INVALID, "prefix table arrays are NULL");
-  }
+  if (!units) return fail(OGS_E_INVALID, "units is NULL");
+  if (int rc = check_routes_args(graph, prefixes, flags)) return rc;
   if (nh_words < 1) {
     return fail(OGS_E_INVALID, "nh_words < 1");
-  }
-  if ((flags & OGS_F_EXACT_ORDER) && !(flags & OGS_F_WIDE_METRIC)) {
-    return fail(OGS_E_INVALID, "OGS_F_EXACT_ORDER needs OGS_F_WIDE_METRIC");
   }
   int unsupported = 0;
   hipError_t e = ogs::launch_spf_routes(
@@ -501,8 +364,7 @@ int ogs_routes_from_spf(const ogs_graph* graph, const ogs_prefix_table* prefixes
   if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
   if (n_units == 0 || prefixes->max_prefixes <= 0) return OGS_OK;
   if (!units || !spf_dist || !spf_nh || !graph->node_base || !graph->node_flags ||
-      !prefixes->pfx_base || !prefixes->adv_off || !prefixes->adv_node ||
-      !prefixes->adv_metrics || !prefixes->adv_min_nh || !prefixes->pfx_flags) {
+      !prefix_arrays_set(prefixes)) {
     return fail(OGS_E_INVALID, "input arrays are NULL");
   }
   if (nh_words < 1) {
@@ -524,16 +386,11 @@ int ogs_ksp_paths(const ogs_graph* graph, const ogs_path_unit* units,
       !out->path_len || !out->path_edges) {
     return fail(OGS_E_INVALID, "graph/unit/output arrays are NULL");
   }
-  if (graph->max_nodes <= 0 ||
-      uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
-    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
-  }
+  if (int rc = check_max_nodes(graph)) return rc;
   if (masks && mask_words < uint32_t((graph->max_edges + 31) / 32)) {
     return fail(OGS_E_INVALID, "mask_words too small for max_edges");
   }
-  if (graph->max_degree >= OGS_MAX_DEGREE && !graph->rslot_ext) {
-    return fail(OGS_E_INVALID, "rows of 512+ edges need graph->rslot_ext");
-  }
+  if (int rc = check_rslot_ext(graph)) return rc;
   int unsupported = 0;
   hipError_t e = ogs::launch_ksp(*graph, units, n_units, masks, mask_words,
                                  flags, *out, static_cast<hipStream_t>(stream),
@@ -560,13 +417,8 @@ int ogs_ksp2_paths(const ogs_graph* graph, const ogs_unit* sources,
       return fail(OGS_E_INVALID, "path output arrays are NULL");
     }
   }
-  if (graph->max_nodes <= 0 ||
-      uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
-    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
-  }
-  if (graph->max_degree >= OGS_MAX_DEGREE && !graph->rslot_ext) {
-    return fail(OGS_E_INVALID, "rows of 512+ edges need graph->rslot_ext");
-  }
+  if (int rc = check_max_nodes(graph)) return rc;
+  if (int rc = check_rslot_ext(graph)) return rc;
   int unsupported = 0;
   hipError_t e = ogs::launch_ksp2(*graph, sources, n_sources, units, n_units,
                                   flags, *k1, *k2,
@@ -587,9 +439,7 @@ int ogs_spf_routes_variants(const ogs_graph* graph,
   if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
   if (n_units == 0) return OGS_OK;
   if (!units || !graph->node_base || !graph->row_ptr || !graph->edges ||
-      !graph->node_flags || !prefixes->pfx_base || !prefixes->adv_off ||
-      !prefixes->adv_node || !prefixes->adv_metrics || !prefixes->adv_min_nh ||
-      !prefixes->pfx_flags) {
+      !graph->node_flags || !prefix_arrays_set(prefixes)) {
     return fail(OGS_E_INVALID, "graph / prefix table arrays are NULL");
   }
   if (mods && (!mods->dead_edges || mods->dead_per_unit < 1 || mods->dead_per_unit > 8)) {
@@ -605,9 +455,7 @@ int ogs_spf_routes_variants(const ogs_graph* graph,
   if ((flags & OGS_F_CHANGED_ONLY) && (!(flags & OGS_F_INCREMENTAL) || nh_words != 1)) {
     return fail(OGS_E_INVALID, "OGS_F_CHANGED_ONLY needs OGS_F_INCREMENTAL and nh_words 1");
   }
-  if (graph->max_nodes <= 0 || uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
-    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
-  }
+  if (int rc = check_max_nodes(graph)) return rc;
   if (nh_words < 1) {
     return fail(OGS_E_INVALID, "nh_words < 1");
   }
@@ -707,9 +555,7 @@ int ogs_routes_multiarea(const ogs_graph* graph,
   if (n_units == 0) return OGS_OK;
   if (!units || !spf_row || !spf_dist || !spf_nh || !graph->node_base ||
       !graph->node_flags || !areas->name_local || !areas->adv_area ||
-      !areas->adv_name || !prefixes->pfx_base || !prefixes->adv_off ||
-      !prefixes->adv_node || !prefixes->adv_metrics || !prefixes->adv_min_nh ||
-      !prefixes->pfx_flags) {
+      !areas->adv_name || !prefix_arrays_set(prefixes)) {
     return fail(OGS_E_INVALID, "multi-area input arrays are NULL");
   }
   if (areas->num_areas <= 0 || areas->num_areas > graph->num_topos) {

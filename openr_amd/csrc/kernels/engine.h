@@ -17,46 +17,63 @@
 
 namespace ogs {
 
-// The defaults and meaning of each knob are documented where it is read
-// (the "EngineOptions::<name>" comments) and in include/openr_gpu.h.
+// $OGS_UNIT_WIDTH seeds "unit_width" (un-validated) each time an
+// EngineOptions is constructed
+inline int unit_width_from_env() {
+  const char* e = std::getenv("OGS_UNIT_WIDTH");
+  return e ? std::atoi(e) : -1;
+}
+
+// Every ogs_set_option knob, stated once: X(name, EngineOptions member,
+// default, accepted values), the accepted values being OGS_RANGE(lo, hi)
+// (inclusive) or OGS_LIST(v, ...); whoever expands that argument defines the
+// two macros. EngineOptions below and the name / validation table of
+// ogs_set_option, ogs_get_option and ogs_option_name (capi.hip) are generated
+// from this list, so a new knob is one line here plus its prose in
+// include/openr_gpu.h. The meaning of each knob is documented where it is
+// read (the "EngineOptions::<name>" comments) and in that header.
+#define OGS_ENGINE_OPTIONS(X)                                              \
+  X(ksp_wave_trace, kspWaveTrace, 1, OGS_LIST(0, 1))                       \
+  X(ksp_hbm, kspHbm, 0, OGS_LIST(0, 1))                                    \
+  X(ksp_queue, kspQueue, 1, OGS_LIST(0, 1))                                \
+  X(ksp_stage, kspStage, -1, OGS_RANGE(-1, 2))                             \
+  X(ksp_prune, kspPrune, 1, OGS_LIST(0, 1))                                \
+  X(route_stream, routeStream, 5, OGS_LIST(1, 2, 4, 5))                    \
+  X(route_store_nt, routeStoreNt, 2, OGS_RANGE(0, 3))                      \
+  X(spf_lane_walk, spfLaneWalk, -1, OGS_RANGE(-1, 1))                      \
+  X(spf_preload, spfPreload, 1, OGS_LIST(0, 1))                            \
+  X(spf_seed_row, spfSeedRow, 1, OGS_LIST(0, 1))                           \
+  X(spf_packed_scan, spfPackedScan, 1, OGS_LIST(0, 1))                     \
+  X(spf_queue, spfQueue, -1, OGS_LIST(-1, 0))                              \
+  X(spf_ninfo, spfNinfo, 1, OGS_RANGE(-1, 1))                              \
+  X(frontier_block, frontierBlock, 0, OGS_LIST(0, 256, 512, 1024))         \
+  X(frontier_parts, frontierParts, 0, OGS_RANGE(0, 16))                    \
+  X(frontier_parts_wide, frontierPartsWide, 0, OGS_RANGE(0, 16))           \
+  X(spf_frontier, spfFrontier, 1, OGS_LIST(0, 1))                          \
+  X(c4_desc, c4Desc, 1, OGS_LIST(0, 1))                                    \
+  X(spf_global, spfGlobal, 0, OGS_LIST(0, 1))                              \
+  X(spf_global_sync, spfGlobalSync, 1, OGS_LIST(0, 1))                     \
+  X(spf_global_lds, spfGlobalLds, 1, OGS_RANGE(0, 3))                      \
+  X(lds_parts, ldsParts, 0, OGS_RANGE(0, 64))                              \
+  X(lds_grid, ldsGrid, 0, OGS_RANGE(0, 4096))                              \
+  X(lds_key16, ldsKey16, 1, OGS_LIST(0, 1))                                \
+  X(lds_tail, ldsTail, 1, OGS_LIST(0, 1))                                  \
+  X(lds_bfs_exit, ldsBfsExit, 1, OGS_LIST(0, 1))                           \
+  X(lds_pull, ldsPull, 6, OGS_RANGE(0, 15))                                \
+  X(lds_lead, ldsLead, 0, OGS_RANGE(-1, 65536))                            \
+  X(lds_tail_parts, ldsTailParts, 0, OGS_RANGE(0, 64))                     \
+  X(ms_group, msGroup, 0, OGS_LIST(0, 1, 2, 4))                            \
+  X(wave_wg_lds, waveWgLds, 0, OGS_RANGE(0, 163840))                       \
+  X(wave_upb, waveUpb, 4, OGS_LIST(4, 8, 16))                              \
+  /* 2: OGS_WAVE_OPT_REG_ROUTES (spf_route_wave.hip) */                    \
+  X(wave_opt, waveOpt, 2, OGS_RANGE(0, 3))                                 \
+  X(unit_width, unitWidth, unit_width_from_env(),                          \
+    OGS_LIST(-1, 0, 1, 2, 3, 64, 128, 256))
+
 struct EngineOptions {
-  int kspWaveTrace = 1;
-  int kspHbm = 0;
-  int kspQueue = 1;
-  int kspStage = -1;
-  int kspPrune = 1;
-  int routeStream = 5;
-  int routeStoreNt = 2;
-  int spfLaneWalk = -1;
-  int spfPreload = 1;
-  int spfSeedRow = 1;
-  int spfPackedScan = 1;
-  int spfQueue = -1;
-  int spfNinfo = 1;
-  int frontierBlock = 0;
-  int frontierParts = 0;
-  int frontierPartsWide = 0;
-  int spfFrontier = 1;
-  int c4Desc = 1;
-  int spfGlobal = 0;
-  int spfGlobalSync = 1;
-  int spfGlobalLds = 1;
-  int ldsParts = 0;
-  int ldsGrid = 0;
-  int ldsKey16 = 1;
-  int ldsTail = 1;
-  int ldsBfsExit = 1;
-  int ldsPull = 6;
-  int ldsLead = 0;
-  int ldsTailParts = 0;
-  int msGroup = 0;
-  int waveWgLds = 0;
-  int waveUpb = 4;
-  int waveOpt = 2;  // OGS_WAVE_OPT_REG_ROUTES (spf_route_wave.hip)
-  int unitWidth = [] {
-    const char* e = std::getenv("OGS_UNIT_WIDTH");
-    return e ? std::atoi(e) : -1;
-  }();
+#define OGS_OPTION_MEMBER(name, member, def, accepted) int member = def;
+  OGS_ENGINE_OPTIONS(OGS_OPTION_MEMBER)
+#undef OGS_OPTION_MEMBER
 };
 
 struct Workspace {

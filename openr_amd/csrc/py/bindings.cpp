@@ -492,18 +492,8 @@ class BatchRunner {
 
   void upload() {
     wide_ |= exact_;  // spf_exact.hip writes 64-bit distances
-    dNodeBase_.upload(hb_.nodeBase.data(), hb_.nodeBase.size());
-    dDesc_.upload(hb_.topoDesc.data(), hb_.topoDesc.size());
-    dRow_.upload(hb_.rowPtr.data(), hb_.rowPtr.size());
-    dEdges_.upload(hb_.edges.data(), hb_.edges.size());
-    dEdgeSrc_.upload(hb_.edgeSrc.data(), hb_.edgeSrc.size());
-    dFlags_.upload(hb_.nodeFlags.data(), hb_.nodeFlags.size());
-    dPfxBase_.upload(hb_.pfxBase.data(), hb_.pfxBase.size());
-    dAdvOff_.upload(hb_.advOff.data(), hb_.advOff.size());
-    dAdvNode_.upload(hb_.advNode.data(), hb_.advNode.size());
-    dAdvMetrics_.upload(hb_.advMetrics.data(), hb_.advMetrics.size());
-    dAdvMinNh_.upload(hb_.advMinNh.data(), hb_.advMinNh.size());
-    dPfxFlags_.upload(hb_.pfxFlags.data(), hb_.pfxFlags.size());
+    img_.uploadGraph(hb_);
+    img_.uploadTable(hb_);
     std::vector<uint16_t> slots;
     std::vector<uint32_t> slotEdges;
     slotStride_ = slotOrder_ ? hb_.slotOrder(slots, &slotEdges, &slotDegree_) : 0;
@@ -524,7 +514,7 @@ class BatchRunner {
 
   void run() {
     ogs_graph g = graph();
-    ogs_prefix_table pt = table();
+    ogs_prefix_table pt = img_.table(hb_);
     ogs_spf_out out{dDist_.get(), dNh_.as<uint32_t>(), dMeta_.as<uint32_t>(),
                     dMetric_.get(), dMask_.as<uint32_t>(),
                     selOut_ ? dSel_.as<uint32_t>() : nullptr,
@@ -659,34 +649,12 @@ class BatchRunner {
 
  private:
   ogs_graph graph() const {
-    ogs_graph g{};
-    g.num_topos = int32_t(topos_.size());
-    g.max_nodes = hb_.maxNodes;
-    g.max_edges = hb_.maxEdges;
-    g.max_degree = hb_.maxDegree;
-    g.topo_desc = dDesc_.as<uint32_t>();
-    g.node_base = dNodeBase_.as<uint32_t>();
-    g.row_ptr = dRow_.as<uint32_t>();
-    g.edges = dEdges_.as<uint64_t>();
-    g.node_flags = dFlags_.as<uint8_t>();
+    ogs_graph g = img_.graph(hb_, int(topos_.size()));  // + this runner's slot image
     g.slot_node = slotStride_ ? dSlot_.as<uint16_t>() : nullptr;
     g.slot_stride = slotStride_;
     g.slot_edges = slotDegree_ ? dSlotEdges_.as<uint32_t>() : nullptr;
     g.slot_degree = slotDegree_;
-    g.edge_src = dEdgeSrc_.as<uint32_t>();
     return g;
-  }
-  ogs_prefix_table table() const {
-    ogs_prefix_table pt{};
-    pt.max_prefixes = hb_.maxPrefixes;
-    pt.max_advertisements = hb_.maxAdvs;
-    pt.pfx_base = dPfxBase_.as<uint32_t>();
-    pt.adv_off = dAdvOff_.as<uint32_t>();
-    pt.adv_node = dAdvNode_.as<uint32_t>();
-    pt.adv_metrics = dAdvMetrics_.as<int32_t>();
-    pt.adv_min_nh = dAdvMinNh_.as<int64_t>();
-    pt.pfx_flags = dPfxFlags_.as<uint8_t>();
-    return pt;
   }
   struct Topo {
     AreaLinkStates als;
@@ -698,16 +666,15 @@ class BatchRunner {
   bool enableV4_, sr_, brs_;
   bool slotOrder_{true}, slotEdgeImage_{true};
   int slotStride_{0}, slotDegree_{0};
-  DeviceBuffer dSlot_, dSlotEdges_, dEdgeSrc_;
+  DeviceBuffer dSlot_, dSlotEdges_;
   std::vector<std::unique_ptr<Topo>> topos_;
   HostBatch hb_;
   std::vector<ogs_unit> units_;
   std::vector<std::string> unitSrc_;
   int W_{1};
   bool wide_{false}, exact_{false};
-  DeviceBuffer dDesc_, dNodeBase_, dRow_, dEdges_, dFlags_, dPfxBase_, dAdvOff_,
-      dAdvNode_, dAdvMetrics_, dAdvMinNh_, dPfxFlags_, dUnits_, dDist_, dNh_,
-      dMeta_, dMetric_, dMask_, dSel_, dReach_;
+  HostBatchImage img_;  // device copy of hb_
+  DeviceBuffer dUnits_, dDist_, dNh_, dMeta_, dMetric_, dMask_, dSel_, dReach_;
   std::vector<uint64_t> dist_, metric_;
   std::vector<uint32_t> nh_, meta_, mask_, sel_, reach_;
 };

@@ -99,17 +99,8 @@ def test_c3_full_every_source_matches_oracle(product, opts):
         pytest.skip("oracle C3 per-source digests incomplete")
     assert set(want) == set(names)
     import openr_amd.capi as capi
-    lib = capi.load()
-    defaults = dict(frontier_block=0, frontier_parts=0, frontier_parts_wide=0, route_stream=5,
-                    lds_parts=0, lds_grid=0, lds_key16=1, lds_tail=1, lds_lead=0,
-                    lds_bfs_exit=1, lds_tail_parts=0, lds_pull=6)
-    for k, v in opts.items():
-        capi.check(lib, lib.ogs_set_option(k.encode(), v), k)
-    try:
+    with capi.scoped_options(**opts):
         launches = _c3(product, names)
-    finally:
-        for k, v in defaults.items():
-            lib.ogs_set_option(k.encode(), v)
     job = 0
     bad = []
     for L in launches:

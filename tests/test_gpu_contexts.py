@@ -187,6 +187,42 @@ def test_two_threads_own_contexts(product):
         lib.ogs_ctx_destroy(ctx_b)
 
 
+def test_ctx_option_read_back():
+    """A fresh context's getter returns the process values (one of them moved
+    off its default first); ogs_ctx_set_option then changes that context's
+    getter only. No launch."""
+    import openr_amd.capi as capi
+    lib = capi.load()
+
+    def ctx_get(ctx, name):
+        v = ctypes.c_int64()
+        capi.check(lib, lib.ogs_ctx_get_option(ctx, name.encode(), ctypes.byref(v)), name)
+        return v.value
+
+    names = []
+    while lib.ogs_option_name(len(names)) is not None:
+        names.append(lib.ogs_option_name(len(names)).decode())
+    assert len(names) == 34
+    with capi.scoped_options(lib, lds_pull=9):
+        process = {n: capi.get_option(lib, n) for n in names}
+        assert process["lds_pull"] == 9
+        ctx_a, ctx_b = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(lib, lib.ogs_ctx_create(0, ctypes.byref(ctx_a)), "ogs_ctx_create")
+        capi.check(lib, lib.ogs_ctx_create(0, ctypes.byref(ctx_b)), "ogs_ctx_create")
+        try:
+            assert {n: ctx_get(ctx_a, n) for n in names} == process
+            capi.check(lib, lib.ogs_ctx_set_option(ctx_a, b"route_stream", 2), "ctx option")
+            capi.check(lib, lib.ogs_ctx_set_option(ctx_a, b"lds_pull", 3), "ctx option")
+            assert lib.ogs_ctx_set_option(ctx_a, b"lds_pull", 16) != 0
+            assert {n: ctx_get(ctx_a, n) for n in names} == \
+                {**process, "route_stream": 2, "lds_pull": 3}
+            assert {n: ctx_get(ctx_b, n) for n in names} == process
+            assert {n: capi.get_option(lib, n) for n in names} == process
+        finally:
+            lib.ogs_ctx_destroy(ctx_a)
+            lib.ogs_ctx_destroy(ctx_b)
+
+
 def _c3_shard_job(product, capi, torch, dev, rank=0, world=8):
     """The C3 fabric (2,080 nodes x 208k prefixes) restricted to the sources
     of one N-rank shard (bench.py's interleave), every width group through

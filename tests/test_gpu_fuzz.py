@@ -10,10 +10,11 @@ LinkState.cpp:789-811) together with overloaded adjacencies and nodes
 (SpfSolver.cpp:139-311, LsdbUtil.cpp:760-823), best-route selection, node
 segment labels and RibPolicy (RibPolicy.cpp:74-161, 222-229), with sources
 that include an unknown node (no RouteDb, SpfSolver.cpp:95-107)."""
-import contextlib
 import random
 
 import pytest
+
+from openr_amd import capi
 
 pytestmark = pytest.mark.gpu
 
@@ -126,30 +127,14 @@ def test_multi_area_feature_sweep(product, oracle, seed):
          f"multiarea {opts} v4={v4} sr={sr} brs={brs} pol={len(pol)}")
 
 
-class _Opt:
-    """Sets an engine option for the block, then restores `reset`."""
-
-    def __init__(self, name, value, reset):
-        import openr_amd.capi as capi
-        self.lib, self.name, self.value, self.reset = capi.load(), name, value, reset
-
-    def __enter__(self):
-        import openr_amd.capi as capi
-        capi.check(self.lib, self.lib.ogs_set_option(self.name, self.value), self.name.decode())
-
-    def __exit__(self, *a):
-        self.lib.ogs_set_option(self.name, self.reset)
-
-
-# kernel-path overrides (option, value, default): the same sweep through the
-# paths the size dispatcher would not pick for these small topologies
+# kernel-path overrides (engine options): the same sweep through the paths
+# the size dispatcher would not pick for these small topologies
 PATHS = {
-    "global_lds0": [(b"spf_global", 1, 0), (b"spf_global_lds", 0, 1)],
-    "global_lds3": [(b"spf_global", 1, 0), (b"spf_global_lds", 3, 1)],
-    "global_hbm_nosync": [(b"spf_global", 1, 0), (b"spf_global_lds", 0, 1),
-                          (b"spf_global_sync", 0, 1)],
-    "workgroup_units": [(b"unit_width", 256, -1)],
-    "wave_plain": [(b"wave_opt", 0, 2)],
+    "global_lds0": dict(spf_global=1, spf_global_lds=0),
+    "global_lds3": dict(spf_global=1, spf_global_lds=3),
+    "global_hbm_nosync": dict(spf_global=1, spf_global_lds=0, spf_global_sync=0),
+    "workgroup_units": dict(unit_width=256),
+    "wave_plain": dict(wave_opt=0),
 }
 
 
@@ -161,9 +146,7 @@ def test_forced_path_feature_sweep(product, oracle, path, seed):
     srcs = rng.sample(names, min(len(names), rng.randint(1, 4))) + ["no-such-node"]
     v4, sr, brs = rng.random() < 0.7, rng.random() < 0.4, rng.random() < 0.5
     pol = _policy(rng, names, ["test_area_name"])
-    with contextlib.ExitStack() as st:
-        for name, value, reset in PATHS[path]:
-            st.enter_context(_Opt(name, value, reset))
+    with capi.scoped_options(**PATHS[path]):
         got = product.gen_route_dbs(kind, opts, srcs, v4, sr, brs, pol)
     _cmp(got, oracle.gen_route_dbs(kind, opts, srcs, v4, sr, brs, pol),
          f"{path}: {kind} {opts} v4={v4} sr={sr} brs={brs} pol={len(pol)}")
@@ -186,7 +169,7 @@ def test_link_failure_variants_feature_sweep(product, oracle, seed, desc):
     base, variants, links = oracle.variant_route_updates(kind, opts, src, n, vseed, 500,
                                                          True, brs)
     label = f"{kind} {opts} src={src} brs={brs}"
-    with _Opt(b"c4_desc", desc, 1):
+    with capi.scoped_options(c4_desc=desc):
         for mode in (0, 1, 2):
             vr = product.VariantRunner(True, brs)
             vr.setup(kind, opts, src, n, vseed, 500)
@@ -208,8 +191,7 @@ def test_link_failure_variants_feature_sweep(product, oracle, seed, desc):
                     assert vr.updated_canonical(v) == canon, f"variant {v} {links[v]}: {label}"
 
 
-KSP_PATHS = [[], [(b"ksp_hbm", 1, 0)], [(b"ksp_wave_trace", 0, 1)], [(b"ksp_queue", 0, 1)],
-             [(b"ksp_prune", 0, 1)]]
+KSP_PATHS = [{}, dict(ksp_hbm=1), dict(ksp_wave_trace=0), dict(ksp_queue=0), dict(ksp_prune=0)]
 
 
 @pytest.mark.parametrize("seed", range(64))
@@ -218,8 +200,9 @@ def test_ksp2_feature_sweep(product, oracle, seed):
     random grids: metric sets with zeros / negatives / large values, parallel
     links (engine and oracle share the canonical link order),
     hard-drained nodes, k = 1..3 single calls and the k = 1, 2 batch, through
-    the default, HBM-state, lane-0-trace, pull-fixpoint and unpruned (full
-    masked rerun) KSP paths."""
+    the default, HBM-state, lane-0-trace and pull-fixpoint KSP paths and with
+    ksp_prune 0 (these grids of at most 64 nodes never reach the pruned
+    masked rerun, so that option changes nothing here)."""
     import test_gpu_ksp_domains as K
     rng = random.Random(0xF05B + seed)
     n = rng.randint(2, 8)
@@ -229,9 +212,7 @@ def test_ksp2_feature_sweep(product, oracle, seed):
     overload = set(rng.sample(range(n * n), rng.randint(0, max(0, n * n // 8))))
     path = KSP_PATHS[seed % len(KSP_PATHS)]
     gseed = rng.getrandbits(16)
-    with contextlib.ExitStack() as st:
-        for name, value, reset in path:
-            st.enter_context(_Opt(name, value, reset))
+    with capi.scoped_options(**path):
         pa, pls = K._grid(product, n, gseed, metrics, parallel, overload)
         oa, ols = K._grid(oracle, n, gseed, metrics, parallel, overload)
         K._check_single(pls, ols, K._pairs(n, 8, gseed), ks=(1, 2, 3))
@@ -272,29 +253,21 @@ def _big_topology(rng):
 @pytest.mark.parametrize("seed", range(40))
 def test_batch_runner_feature_sweep(product, oracle, seed):
     """Many sources of one random topology in ONE BatchRunner launch, under a
-    random choice of the large-topology forms (route_stream 0 / 1 / 2,
+    random choice of the large-topology forms (route_stream 1 / 2 / 4 / 5,
     spf_frontier 0 / 1, ms_group 0 / 1 / 2 / 4)."""
-    import openr_amd.capi as capi
     rng = random.Random(0xFBA7 + seed)
     kind, opts, names = _big_topology(rng)
     srcs = rng.sample(names, min(len(names), rng.randint(1, 12)))
     v4, brs = rng.random() < 0.7, rng.random() < 0.5
     options = dict(route_stream=rng.choice([1, 2, 4, 5]), spf_frontier=rng.choice([0, 1]),
                    ms_group=rng.choice([0, 1, 2, 4]))
-    lib = capi.load()
-    try:
-        for k, v in options.items():
-            capi.check(lib, lib.ogs_set_option(k.encode(), v), k)
+    with capi.scoped_options(**options):
         br = product.BatchRunner(v4, False, brs)
         br.add_generated(kind, opts, srcs)
         br.upload()
         br.run()
         br.download()
         got = [br.canonical(u) for u in range(len(srcs))]
-    finally:
-        lib.ogs_set_option(b"route_stream", 5)
-        lib.ogs_set_option(b"spf_frontier", 1)
-        lib.ogs_set_option(b"ms_group", 0)
     _cmp(got, oracle.gen_route_dbs(kind, opts, srcs, v4, False, brs),
          f"batch {kind} {opts} {options} v4={v4} brs={brs}")
 

@@ -11,6 +11,8 @@ import pytest
 
 import lsdb as L
 
+from openr_amd import capi
+
 pytestmark = pytest.mark.gpu
 
 
@@ -23,37 +25,7 @@ def _cmp(a, b, label):
             pytest.fail(f"{label}[{i}] differs: {diff} (len {len(xa)} vs {len(ya)})")
 
 
-class _Global:
-    """Forces (on=1) or leaves automatic (on=0) the global path."""
-
-    def __init__(self, on):
-        import openr_amd.capi as capi
-        self.lib, self.on = capi.load(), on
-
-    def __enter__(self):
-        import openr_amd.capi as capi
-        capi.check(self.lib, self.lib.ogs_set_option(b"spf_global", self.on), "spf_global")
-
-    def __exit__(self, *a):
-        self.lib.ogs_set_option(b"spf_global", 0)
-
-
 MIX = dict(v4Permille=150, anycastPermille=120, minNhPermille=60, drainPermille=50)
-
-
-class _Opt:
-    """Sets an engine option for the block, then restores `reset`."""
-
-    def __init__(self, name, value, reset):
-        import openr_amd.capi as capi
-        self.lib, self.name, self.value, self.reset = capi.load(), name, value, reset
-
-    def __enter__(self):
-        import openr_amd.capi as capi
-        capi.check(self.lib, self.lib.ogs_set_option(self.name, self.value), self.name.decode())
-
-    def __exit__(self, *a):
-        self.lib.ogs_set_option(self.name, self.reset)
 
 
 @pytest.mark.parametrize("lds", [0, 1, 2, 3])
@@ -69,7 +41,7 @@ def test_forced_global_both_state_forms(product, oracle, lds):
     fab = dict(pods=4, planes=4, sswPerPlane=8, rswPerPod=16, full=True, prefixesPerNode=2,
                nodeOverloadPermille=20, **MIX)
     fsrc = ["1-0-0", "2-1-2", "3-3-15", "2-0-0"]
-    with _Global(1), _Opt(b"spf_global_lds", lds, 1):
+    with capi.scoped_options(spf_global=1, spf_global_lds=lds):
         for opts, label in ((grid, "grid"), (wide, "wide")):
             srcs = [str(i) for i in range(0, 81, 4)]
             _cmp(product.gen_route_dbs("grid", opts, srcs, True, True, True),
@@ -83,7 +55,7 @@ def test_forced_global_grid_all_sources(product, oracle, brs):
     opts = dict(n=7, metricSeed=0xC2000077, prefixSeed=5, adjOverloadPermille=30,
                 nodeOverloadPermille=20, overloadSeed=0x77, **MIX)
     srcs = [str(i) for i in range(49)]
-    with _Global(1):
+    with capi.scoped_options(spf_global=1):
         a = product.gen_route_dbs("grid", opts, srcs, True, True, brs)
     _cmp(a, oracle.gen_route_dbs("grid", opts, srcs, True, True, brs), "grid7")
 
@@ -93,7 +65,7 @@ def test_forced_global_distance_widths(product, oracle, metric_max):
     """u32 and u64 (OGS_F_WIDE_METRIC) distances through the global path."""
     opts = dict(n=10, metricSeed=0xC2300000, prefixSeed=0xC1, metricMax=metric_max)
     srcs = ["1", "45", "99"]
-    with _Global(1):
+    with capi.scoped_options(spf_global=1):
         a = product.gen_route_dbs("grid", opts, srcs, True, True, False)
     _cmp(a, oracle.gen_route_dbs("grid", opts, srcs, True, True, False), "gridw")
 
@@ -107,7 +79,7 @@ def test_forced_global_fabric_prefix_mix(product, oracle):
              [f"2-{p}-{f}" for p in range(8) for f in range(4)] +
              [f"3-{p}-{r}" for p in range(8) for r in range(32)])
     srcs = names[::9] + ["2-5-1"]
-    with _Global(1):
+    with capi.scoped_options(spf_global=1):
         a = product.gen_route_dbs("fabric", opts, srcs, True, True, False)
     _cmp(a, oracle.gen_route_dbs("fabric", opts, srcs, True, True, False), "fabric")
 
@@ -119,7 +91,7 @@ def test_forced_global_wan_spf_results(product, oracle):
                 adjOverloadPermille=20)
     rng = random.Random(3)
     srcs = [str(rng.randrange(700)) for _ in range(6)]
-    with _Global(1):
+    with capi.scoped_options(spf_global=1):
         a = product.gen_route_dbs("wan", opts, srcs, True, True, True)
     _cmp(a, oracle.gen_route_dbs("wan", opts, srcs, True, True, True), "wan700")
 
@@ -157,7 +129,7 @@ def test_stress_grid_99(product, oracle, force):
     n = 99
     pa, pp = _stress_grid(product, n)
     oa, op = _stress_grid(oracle, n)
-    with _Global(force):
+    with capi.scoped_options(spf_global=force):
         got = product.SpfSolver("1", False, True, True).buildRouteDb("523", pa, pp)
     want = oracle.SpfSolver("1", False, True, True).buildRouteDb("523", oa, op)
     assert got.canonical() == want.canonical()

@@ -73,9 +73,7 @@ def test_groups_match_per_group_calls(product, route_stream, lead):
         return o, so
 
     stream = torch.cuda.current_stream()
-    try:
-        capi.check(lib, lib.ogs_set_option(b"route_stream", route_stream), "route_stream")
-        capi.check(lib, lib.ogs_set_option(b"lds_lead", lead), "lds_lead")
+    with capi.scoped_options(lib, route_stream=route_stream, lds_lead=lead):
         units = [u.contiguous().view(-1).to(dev) for u, _, _ in specs]
         grouped = [outs(len(u) // 2, W, rows) for u, (_, W, rows) in zip(units, specs)]
         arr = (capi.RouteGroup * 3)()
@@ -98,9 +96,6 @@ def test_groups_match_per_group_calls(product, route_stream, lead):
                        "ogs_spf_routes")
             single.append(o)
         torch.cuda.synchronize()
-    finally:
-        lib.ogs_set_option(b"route_stream", 5)
-        lib.ogs_set_option(b"lds_tail_parts", 0)
     for i, ((o, _), s) in enumerate(zip(grouped, single)):
         for k in o:
             assert torch.equal(o[k], s[k]), f"group {i} (W={specs[i][1]}) array {k} differs"

@@ -20,22 +20,9 @@ import pytest
 
 import lsdb as L
 
+from openr_amd import capi
+
 pytestmark = pytest.mark.gpu
-
-
-class _Hbm:
-    """Forces (on=1) or leaves automatic (on=0) the HBM-state KSP path."""
-
-    def __init__(self, on):
-        import openr_amd.capi as capi
-        self.lib, self.on = capi.load(), on
-
-    def __enter__(self):
-        import openr_amd.capi as capi
-        capi.check(self.lib, self.lib.ogs_set_option(b"ksp_hbm", self.on), "ksp_hbm")
-
-    def __exit__(self, *a):
-        self.lib.ogs_set_option(b"ksp_hbm", 0)
 
 
 def _grid(M, n, seed, metrics, parallel=False, overload=()):
@@ -130,7 +117,7 @@ def test_forced_hbm_path_matches_oracle(product, oracle, parallel):
     """Positive metrics through the HBM-state path (option ksp_hbm): single
     calls with masked reruns and the batch, overloads included."""
     n = 7
-    with _Hbm(1):
+    with capi.scoped_options(ksp_hbm=1):
         pa, pls = _grid(product, n, 14, [1, 2, 3, 5], parallel, overload={10, 30})
         oa, ols = _grid(oracle, n, 14, [1, 2, 3, 5], parallel, overload={10, 30})
         _check_single(pls, ols, _pairs(n, 15, 3))
@@ -142,7 +129,7 @@ def test_forced_hbm_wide_distances(product, oracle):
     width, as for buildRouteDb) on the HBM path."""
     n = 12
     big = [21_000_000, 20_999_999, 15_000_000]
-    with _Hbm(1):
+    with capi.scoped_options(ksp_hbm=1):
         pa, pls = _grid(product, n, 15, big)
         oa, ols = _grid(oracle, n, 15, big)
         _check_single(pls, ols, _pairs(n, 10, 4))

@@ -86,11 +86,8 @@ def test_deep_line_with_island_batch(product, oracle, options, uniform):
     the LDS form runs BFS layers (300 of them) and, with the island never
     reached, must not take the all-reached exit."""
     import openr_amd.capi as capi
-    lib = capi.load()
     als, ps = _build(product, uniform)
-    try:
-        for k, v in options.items():
-            capi.check(lib, lib.ogs_set_option(k.encode(), v), k)
+    with capi.scoped_options(**options):
         solver = product.SpfSolver(SOURCES[0], True, False)
         batch = product.RouteDbBatch(solver, als, ps, SOURCES)
         batch.launch()
@@ -98,13 +95,6 @@ def test_deep_line_with_island_batch(product, oracle, options, uniform):
         for s in SOURCES:
             db = batch.routeDb(s)
             got.append(b"NONE" if db is None else db.canonical())
-    finally:
-        lib.ogs_set_option(b"route_stream", 5)
-        lib.ogs_set_option(b"spf_queue", -1)
-        lib.ogs_set_option(b"lds_bfs_exit", 1)
-        lib.ogs_set_option(b"lds_lead", 0)
-        lib.ogs_set_option(b"lds_tail_parts", 0)
-        lib.ogs_set_option(b"lds_pull", 6)
     want = _oracle(oracle, uniform)
     # the island's anycast member is unreachable from the line: the line's
     # end must be the prefix's only route source

@@ -201,10 +201,9 @@ def test_c2_kernel_variants_identical(product, oracle, brs):
     opts = dict(n=10, metricSeed=0xC2200000, prefixSeed=0xC1,
                 adjOverloadPermille=10, nodeOverloadPermille=20, overloadSeed=0xC22F)
     cpu = None
-    try:
-        for uw in (0, 1, 2, 3, 128):
-            for order, image in ((True, True), (True, False), (False, False)):
-                capi.check(lib, lib.ogs_set_option(b"unit_width", uw), "unit_width")
+    for uw in (0, 1, 2, 3, 128):
+        for order, image in ((True, True), (True, False), (False, False)):
+            with capi.scoped_options(lib, unit_width=uw):
                 br = product.BatchRunner(True, False, brs)
                 br.set_slot_order(order)
                 br.set_slot_edge_image(image)
@@ -213,11 +212,9 @@ def test_c2_kernel_variants_identical(product, oracle, brs):
                 br.run()
                 br.download()
                 gpu = [br.canonical(u) for u in range(T)]
-                if cpu is None:
-                    cpu = oracle.grid_batch_route_dbs(opts, 0, T, "1", brs)
-                _cmp(gpu, cpu, f"c2 uw={uw} order={order} image={image}")
-    finally:
-        lib.ogs_set_option(b"unit_width", -1)
+            if cpu is None:
+                cpu = oracle.grid_batch_route_dbs(opts, 0, T, "1", brs)
+            _cmp(gpu, cpu, f"c2 uw={uw} order={order} image={image}")
 
 
 @pytest.mark.parametrize("metric_max", [85000, 200000, 20000000])
@@ -246,16 +243,13 @@ def test_wave_store_flavours(product, oracle, nt):
     lib = capi.load()
     opts = dict(n=10, metricSeed=0xC2400077, prefixSeed=0xC1, metricMax=64)
     cpu = oracle.grid_batch_route_dbs(opts, 0, 48, "3")
-    try:
-        capi.check(lib, lib.ogs_set_option(b"route_store_nt", nt), "route_store_nt")
+    with capi.scoped_options(lib, route_store_nt=nt):
         br = product.BatchRunner(True, False, False)
         br.add_grid_batch(opts, 0, 48, "3")
         br.upload()
         br.run()
         br.download()
         got = [br.canonical(u) for u in range(br.num_units())]
-    finally:
-        lib.ogs_set_option(b"route_store_nt", 2)
     _cmp(got, cpu, f"wave store nt={nt}")
 
 
@@ -314,16 +308,13 @@ def test_multi_source_kernel_fabric_all_sources(product, oracle, group):
              [f"2-{p}-{f}" for p in range(8) for f in range(4)] +
              [f"3-{p}-{r}" for p in range(8) for r in range(32)])
     srcs = names[::3] + ["2-5-1", "1-3-15"]
-    try:
-        capi.check(lib, lib.ogs_set_option(b"ms_group", group), "ms_group")
+    with capi.scoped_options(lib, ms_group=group):
         br = product.BatchRunner(True, False, False)
         br.add_generated("fabric", opts, srcs)
         br.upload()
         br.run()
         br.download()
         a = [br.canonical(u) for u in range(len(srcs))]
-    finally:
-        lib.ogs_set_option(b"ms_group", 0)
     _cmp(a, oracle.gen_route_dbs("fabric", opts, srcs, True, False, False), "fabric352")
 
 
@@ -343,32 +334,13 @@ def _batch_dbs(product, kind, opts, srcs, enable_v4, brs, **options):
     """All sources of one generated topology in ONE BatchRunner launch, with
     engine options set for the duration of the call."""
     import openr_amd.capi as capi
-    lib = capi.load()
-    try:
-        for k, v in options.items():
-            capi.check(lib, lib.ogs_set_option(k.encode(), v), k)
+    with capi.scoped_options(**options):
         br = product.BatchRunner(enable_v4, False, brs)
         br.add_generated(kind, opts, srcs)
         br.upload()
         br.run()
         br.download()
         return [br.canonical(u) for u in range(len(srcs))]
-    finally:
-        lib.ogs_set_option(b"route_stream", 5)
-        lib.ogs_set_option(b"lds_parts", 0)
-        lib.ogs_set_option(b"lds_grid", 0)
-        lib.ogs_set_option(b"lds_key16", 1)
-        lib.ogs_set_option(b"lds_tail", 1)
-        lib.ogs_set_option(b"lds_lead", 0)
-        lib.ogs_set_option(b"lds_bfs_exit", 1)
-        lib.ogs_set_option(b"lds_tail_parts", 0)
-        lib.ogs_set_option(b"lds_pull", 6)
-        lib.ogs_set_option(b"frontier_parts", 0)
-        lib.ogs_set_option(b"frontier_parts_wide", 0)
-        lib.ogs_set_option(b"spf_frontier", 1)
-        lib.ogs_set_option(b"ms_group", 0)
-        lib.ogs_set_option(b"route_store_nt", 2)
-        lib.ogs_set_option(b"spf_seed_row", 1)
 
 
 MIX = dict(v4Permille=150, anycastPermille=120, minNhPermille=60, drainPermille=50)
@@ -477,13 +449,7 @@ def test_frontier_packed_chunk_scan(product, oracle, packed, kind):
         rng = random.Random(13)
         srcs = [str(rng.randrange(900)) for _ in range(12)]
         extra = dict(spf_queue=0)
-    try:
-        a = _batch_dbs(product, kind, opts, srcs, True, True, spf_packed_scan=packed, **extra)
-    finally:
-        import openr_amd.capi as capi
-        lib = capi.load()
-        lib.ogs_set_option(b"spf_packed_scan", 1)
-        lib.ogs_set_option(b"spf_queue", -1)
+    a = _batch_dbs(product, kind, opts, srcs, True, True, spf_packed_scan=packed, **extra)
     _cmp(a, oracle.gen_route_dbs(kind, opts, srcs, True, False, True), f"{kind} packed={packed}")
 
 

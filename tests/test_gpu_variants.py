@@ -128,8 +128,7 @@ def test_queue_forms_node_info_option(product, oracle, ninfo):
     kind, opts = "wan", dict(nodes=400, seed=0xC5, prefixesPerNode=1, nodeOverloadPermille=20,
                              adjOverloadPermille=20, anycastPermille=100, minNhPermille=50,
                              drainPermille=50)
-    try:
-        capi.check(lib, lib.ogs_set_option(b"spf_ninfo", ninfo), "spf_ninfo")
+    with capi.scoped_options(lib, spf_ninfo=ninfo):
         vr = product.VariantRunner(True, True)
         vr.setup(kind, opts, "7", 32, 0xC4F, 500)
         vr.launch(0, True)
@@ -142,8 +141,6 @@ def test_queue_forms_node_info_option(product, oracle, ninfo):
         srcs = [str(i) for i in range(0, 400, 37)]
         got, _, _ = product.gen_route_db_batch(kind, opts, srcs, True, True, True)
         assert got == oracle.gen_route_dbs(kind, opts, srcs, True, True, True)
-    finally:
-        lib.ogs_set_option(b"spf_ninfo", 1)
 
 
 def test_route_updates_wide_source(product, oracle):
@@ -230,8 +227,7 @@ def test_repair_large_wan(product, oracle, mode, desc):
     n = 24
     base, variants, links = oracle.variant_route_updates("wan", opts, "5", n, 0xC4F, 500,
                                                          True, False)
-    capi.check(lib, lib.ogs_set_option(b"c4_desc", desc), "c4_desc")
-    try:
+    with capi.scoped_options(lib, c4_desc=desc):
         vr = product.VariantRunner(True, False)
         vr.setup("wan", opts, "5", n, 0xC4F, 500)
         assert vr.shape()["nodes"] == 9500
@@ -248,8 +244,6 @@ def test_repair_large_wan(product, oracle, mode, desc):
                 upd, dele = vr.update(v)
                 assert sorted(upd + dele) == changed, f"variant {v} {links[v]}"
                 assert vr.updated_canonical(v) == canon, f"variant {v} {links[v]}"
-    finally:
-        lib.ogs_set_option(b"c4_desc", 1)
     assert any(changed for _, changed, _, _ in variants)
 
 
@@ -269,15 +263,12 @@ def test_repair_desc_cache_across_launches(product, oracle, first, second):
     vr = product.VariantRunner(True, False)
     vr.setup("wan", opts, "3", n, 0xC4F, 500)
     vr.set_mode(2)
-    try:
-        for desc in (first, second):
-            capi.check(lib, lib.ogs_set_option(b"c4_desc", desc), "c4_desc")
+    for desc in (first, second):
+        with capi.scoped_options(lib, c4_desc=desc):
             vr.launch(0, True)
             vr.fetch_updates(0)
             for v, (canon, changed, nu, nd) in enumerate(variants):
                 upd, dele = vr.update(v)
                 assert sorted(upd + dele) == changed, (desc, v, links[v])
                 assert vr.updated_canonical(v) == canon, (desc, v, links[v])
-    finally:
-        lib.ogs_set_option(b"c4_desc", 1)
     assert any(changed for _, changed, _, _ in variants)

@@ -22,15 +22,6 @@ from openr_amd import shard  # noqa: E402
 from openr_amd.workloads import c3_source_names  # noqa: E402
 
 
-# engine defaults (capi.hip / the kernels' g_* globals) of the options A/B'd here
-DEFAULTS = {"frontier_block": 0, "frontier_parts": 0, "route_stream": 5,
-            "spf_packed_scan": 1, "spf_seed_row": 1, "frontier_parts_wide": 0,
-            "route_store_nt": 2, "spf_lane_walk": -1, "spf_preload": 1,
-            "lds_parts": 0, "lds_grid": 0, "lds_key16": 1, "lds_tail": 1,
-            "lds_bfs_exit": 1, "lds_lead": 0, "lds_tail_parts": 0,
-            "lds_pull": 6}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("variants", nargs="+")
@@ -62,16 +53,15 @@ def main():
     libs = {"": lib}
     if any("lib=base" in v for v in a.variants):
         libs["base"] = capi.load(os.path.join(ROOT, "openr_amd", "lib", "libopenr_gpu_base.so"))
-    unknown = keys - set(DEFAULTS)
-    if unknown:
-        raise SystemExit(f"no default known for {sorted(unknown)}: add it to DEFAULTS")
+    # the values this process started with (an unknown name fails here)
+    defaults = {k: capi.get_option(lib, k) for k in keys}
 
     def apply(v):
         """Sets variant v's options; returns the library it runs through."""
         use = libs["base"] if "lib=base" in v else lib
         bench.C3_GROUPS[0] = "c3groups=0" not in v
         for k in keys:
-            use.ogs_set_option(k.encode(), DEFAULTS[k])  # the base may lack newer knobs
+            use.ogs_set_option(k.encode(), defaults[k])  # the base may lack newer knobs
         for kv in filter(None, v.split(",")):
             k, x = kv.split("=")
             if k not in ("lib", "c3groups"):

@@ -19,7 +19,7 @@ def main():
     from openr_amd import shard
     from openr_amd.workloads import G1_OPTS, G1_SOURCES
     openr_amd.require_gpu()
-    opt = os.environ.get("OPT", "spf_global_sync").encode()
+    opt = os.environ.get("OPT", "spf_global_sync")
     vals = [int(x) for x in os.environ.get("VALS", "0,1").split(",")]
     lib = capi.load()
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_digests.json"))).get("g1")
@@ -29,20 +29,19 @@ def main():
     times = {v: [] for v in vals}
     for rnd in range(6):
         for v in vals:
-            capi.check(lib, lib.ogs_set_option(opt, v), opt.decode())
-            t0 = time.perf_counter()
-            br.run()
-            dt = time.perf_counter() - t0
+            with capi.scoped_options(lib, **{opt: v}):
+                t0 = time.perf_counter()
+                br.run()
+                dt = time.perf_counter() - t0
             if rnd >= 1:
                 times[v].append(dt)
             if rnd == 5:
                 br.download()
                 d = shard.combine_digests(br.unit_digest(u, G1_SOURCES[u])
                                           for u in range(len(G1_SOURCES)))
-                print(f"{opt.decode()}={v}: median {median(times[v]) * 1e3:.3f} ms "
+                print(f"{opt}={v}: median {median(times[v]) * 1e3:.3f} ms "
                       f"min {min(times[v]) * 1e3:.3f} ms digest {d:016x} "
                       f"golden={'match' if f'{d:016x}' == golden else 'MISMATCH'}", flush=True)
-    capi.check(lib, lib.ogs_set_option(opt, 1 if opt == b"spf_global_sync" else 0), "reset")
 
 
 if __name__ == "__main__":
