@@ -27,7 +27,9 @@ $(CCONS): tests/c_consumer/spf_square.c include/openr_gpu.h $(LIB)
 	  -Wl,-rpath,'$$ORIGIN/../../openr_amd/lib'
 
 
-# one object per kernel translation unit (parallel make), then one link
+# one object per kernel translation unit (parallel make), then one link;
+# -z defs: a launch function declared in launch.h but defined nowhere fails
+# the link, not the first call
 KOBJ := $(patsubst openr_amd/csrc/kernels/%.hip,build/kernels/%.o,$(KERNELS))
 
 # each object leaves its kernels' resource report (VGPRs, scratch, occupancy)
@@ -39,7 +41,7 @@ build/kernels/%.o: openr_amd/csrc/kernels/%.hip $(KERNEL_H) include/openr_gpu.h
 
 $(LIB): $(KOBJ)
 	@mkdir -p openr_amd/lib
-	$(HIPCC) --offload-arch=$(ARCH) -shared $(KOBJ) -o $@.tmp && mv -f $@.tmp $@
+	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-z,defs $(KOBJ) -o $@.tmp && mv -f $@.tmp $@
 
 $(MOD): $(HOST) $(HOST_H) openr_amd/csrc/py/bindings.cpp $(LIB)
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -Wno-unused-function \
@@ -60,7 +62,7 @@ build/stamps/%.o: openr_amd/csrc/kernels/%.hip $(KERNEL_H) include/openr_gpu.h
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -DOGS_STAMPS -Iinclude -c $< -o $@
 $(STAMPS): $(SOBJ)
 	@mkdir -p openr_amd/lib
-	$(HIPCC) --offload-arch=$(ARCH) -shared $(SOBJ) -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-z,defs $(SOBJ) -o $@
 
 # CPU sanitizer build (AddressSanitizer + UBSan) of the drop-in's host code
 # (tests/asan/host_asan.cpp over a host-only C-ABI stub, no device) and of

@@ -10,50 +10,7 @@
 
 #include "openr_gpu.h"
 #include "engine.h"
-
-namespace ogs {
-hipError_t launch_spf_routes(const ogs_graph& g, const ogs_prefix_table* pt,
-                             const ogs_unit* units, int nUnits, uint32_t flags,
-                             int W, const ogs_spf_out& out, hipStream_t stream,
-                             int* unsupported);
-hipError_t launch_spf_routes_groups(const ogs_graph& g, const ogs_prefix_table* pt,
-                                    const ogs_route_group* groups, int n, uint32_t flags,
-                                    hipStream_t stream, int* unsupported);
-hipError_t launch_routes_multiarea(const ogs_graph& g, const ogs_prefix_table& pt,
-                                   const ogs_area_table& at,
-                                   const uint32_t* units, int n,
-                                   const uint32_t* spfRow, const void* dist,
-                                   const uint32_t* nh, uint32_t flags, int W,
-                                   const ogs_spf_out& out, hipStream_t stream);
-hipError_t launch_variants(const ogs_graph& g, const ogs_prefix_table& pt,
-                           const ogs_unit* units, int nUnits,
-                           const ogs_unit_mods* mods, ogs_route_diff* diff,
-                           uint32_t flags, int W, const ogs_spf_out& out,
-                           hipStream_t stream, int* unsupported);
-hipError_t launch_rib_policy(const ogs_prefix_table& pt, const ogs_rib_policy& pol,
-                             int A, int nUnits, int W, const uint32_t* meta,
-                             uint32_t* mask, uint16_t* applied, uint16_t* counter,
-                             hipStream_t stream);
-hipError_t launch_route_changes(const uint32_t* changed, int nUnits, int Sp, int W,
-                                const uint32_t* meta, const uint32_t* metric,
-                                const uint32_t* mask, const ogs_route_changes& out,
-                                hipStream_t stream);
-hipError_t launch_csr_patch(uint64_t* edges, const uint32_t* idx, const uint64_t* val,
-                            int n, hipStream_t stream);
-hipError_t launch_routes_from_spf(const ogs_graph& g, const ogs_prefix_table& pt,
-                                  const ogs_unit* units, int n, const void* dist,
-                                  const uint32_t* nh, const uint32_t* reach, uint32_t flags,
-                                  int W, const ogs_spf_out& out, hipStream_t stream);
-hipError_t launch_ksp(const ogs_graph& g, const ogs_path_unit* units,
-                      int nUnits, const uint32_t* masks, uint32_t maskWords,
-                      uint32_t flags, const ogs_path_out& out,
-                      hipStream_t stream, int* unsupported);
-hipError_t launch_ksp2(const ogs_graph& g, const ogs_unit* sources,
-                       int nSources, const ogs_path_unit* units, int nUnits,
-                       uint32_t flags, const ogs_path_out& o1,
-                       const ogs_path_out& o2, hipStream_t stream,
-                       int* unsupported);
-}
+#include "launch.h"
 
 namespace {
 thread_local std::string g_lastError;

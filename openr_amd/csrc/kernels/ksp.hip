@@ -24,6 +24,7 @@
 #include "openr_gpu.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -370,16 +371,9 @@ hipError_t ksp_launch(const ogs_graph& g, const ogs_path_unit* units,
   constexpr int upb = kBlock / UT;
   const int grid = (nUnits + upb - 1) / upb;
   const size_t bytes = size_t(lds) * upb;
-  auto k = ksp_kernel<D, UT, STAGE, MASKED>;
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k),
-        hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), bytes, stream, g, units,
-                     nUnits, masks, maskWords, out, lds, opts().kspWaveTrace);
-  return hipGetLastError();
+  return launch_dyn_lds(ksp_kernel<D, UT, STAGE, MASKED>, dim3(grid), dim3(kBlock), bytes,
+                        stream, g, units, nUnits, masks, maskWords, out, lds,
+                        opts().kspWaveTrace);
 }
 
 // ---- HBM-state KSP: units past the LDS budget, and the exact order -------
@@ -407,22 +401,8 @@ constexpr uint32_t kRankNew = 0xFFFFFFFFu;   // never inserted
 constexpr uint32_t kRankOpen = 0xFFFFFFFEu;  // in the open list
 // EngineOptions::kspHbm (engine.h), default 0  // "ksp_hbm" option: 1 = every KSP unit on the HBM path
 
-hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
-
-// A unit's workgroup runs on one CU: its HBM state stays in that XCD's L2
-// for the whole launch. Rounds end with every wave's stores drained and a
-// barrier; state written in this launch is read back through sc1 (L2-served,
-// L1-bypassing) loads -- the L1 may hold lines that L2 atomics have since
-// changed (MI355X_MICROARCH.md, inter-workgroup visibility).
-__device__ __forceinline__ void hbm_block_sync() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-template <typename T>
-__device__ __forceinline__ T ld_l2(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// The unit's HBM state is synchronised and read back as spf_core.h's
+// round_sync<true> / ld_state<true> describe.
 
 __device__ __forceinline__ void hbm_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -455,16 +435,16 @@ __device__ void frontier_dist_hbm(uint32_t N, uint32_t s, const UnitCsr& c,
     qcnt[1] = 1u;
     qcnt[2] = 0u;
   }
-  hbm_block_sync();
+  round_sync<true>();
   uint32_t n = 1;
   for (uint32_t r = 1; n; ++r) {
     if (tid == 0) qcnt[(r + 2) % 3] = 0u;
     const uint32_t* cur = (r & 1) ? q1 : q0;
     uint32_t* nxt = (r & 1) ? q0 : q1;
     for (uint32_t i = tid; i < n; i += kKspHbmBlock) {
-      const uint32_t v = ld_l2(cur + i);
+      const uint32_t v = ld_state<true>(cur + i);
       if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
-      const D dv = ld_l2(dist + v);
+      const D dv = ld_state<true>(dist + v);
       const uint32_t rEnd = c.rowp[v + 1];
       for (uint32_t e = c.rowp[v]; e < rEnd; ++e) {
         const uint64_t ed = c.edg[e];
@@ -476,14 +456,14 @@ __device__ void frontier_dist_hbm(uint32_t N, uint32_t s, const UnitCsr& c,
         }
         const uint32_t t = edge_dst(lo);
         const D cand = dv + static_cast<D>(static_cast<uint32_t>(ed >> 32));
-        if (cand < ld_l2(dist + t) && cand < atomicMin(&dist[t], cand)) {
+        if (cand < ld_state<true>(dist + t) && cand < atomicMin(&dist[t], cand)) {
           if (atomicMax(&stamp[t], r + 1) < r + 1) {
             nxt[atomicAdd(&qcnt[(r + 1) % 3], 1u)] = t;
           }
         }
       }
     }
-    hbm_block_sync();
+    round_sync<true>();
     n = qcnt[(r + 1) % 3];
     __syncthreads();  // every thread has read the count before it is reset
   }
@@ -616,14 +596,14 @@ __device__ uint32_t trace_paths_hbm(const UnitCsr& csr, const D* dist, const uin
       hi = rank[u];
       lo = slot;
     } else {
-      hi = static_cast<uint64_t>(ld_l2(dist + u));
+      hi = static_cast<uint64_t>(ld_state<true>(dist + u));
       lo = csr.rowp[u] + slot;  // (u, slot) order for rows of any length
     }
   };
   uint32_t* pathLen = out.path_len + row * out.max_paths;
   uint32_t* pathEdges = out.path_edges + row * out.max_edges;
   uint32_t nPaths = 0, nEdges = 0, status = 0;
-  const bool reachable = (s != t) && (EXACT ? rank[t] < kRankOpen : ld_l2(dist + t) != kInf);
+  const bool reachable = (s != t) && (EXACT ? rank[t] < kRankOpen : ld_state<true>(dist + t) != kInf);
   while (reachable) {
     int sp = 0;
     if (lane == 0) stack[0] = Frame{t, 0xFFFFFFFFu};
@@ -632,7 +612,7 @@ __device__ uint32_t trace_paths_hbm(const UnitCsr& csr, const D* dist, const uin
     while (sp >= 0) {
       const Frame f = stack[sp];
       const uint32_t v = f.node;
-      const D dv = ld_l2(dist + v);
+      const D dv = ld_state<true>(dist + v);
       const uint32_t rv = EXACT ? rank[v] : 0u;
       const bool fresh = f.edge == 0xFFFFFFFFu;
       uint64_t lastHi = 0;
@@ -660,7 +640,7 @@ __device__ uint32_t trace_paths_hbm(const UnitCsr& csr, const D* dist, const uin
             }
           }
           if (ok) {
-            const D du = ld_l2(dist + u);
+            const D du = ld_state<true>(dist + u);
             bool tight;
             if constexpr (EXACT) {
               tight = rank[u] < rv && du + ksp_exact_weight(ed) == dv;
@@ -844,7 +824,7 @@ __global__ __launch_bounds__(EXACT ? 64 : kKspHbmBlock) void ksp_hbm_kernel(
     } else {
       frontier_dist_hbm<D, M>(N, s, csr, nflags, dist, aux, q0, q1, qcnt, ignore);
     }
-    hbm_block_sync();
+    round_sync<true>();
   };
   spf(ign, std::integral_constant<bool, MASKED>{});
   uint32_t c1 = 0;
@@ -855,7 +835,7 @@ __global__ __launch_bounds__(EXACT ? 64 : kKspHbmBlock) void ksp_hbm_kernel(
   }
   if constexpr (TWO) {
     if (tid == 0) bcast = c1;
-    hbm_block_sync();
+    round_sync<true>();
     c1 = bcast;
     // k = 1 found nothing: linksToIgnore is empty, k = 2 finds nothing
     // either; a k = 1 overflow leaves the mask incomplete (reported)
@@ -864,7 +844,7 @@ __global__ __launch_bounds__(EXACT ? 64 : kKspHbmBlock) void ksp_hbm_kernel(
       return;
     }
     for (uint32_t i = tid; i < linkWords; i += nt) visited[i] = 0u;
-    hbm_block_sync();
+    round_sync<true>();
     spf(mask, std::integral_constant<bool, true>{});
     if (tid < 64) {
       const uint32_t c2 = trace_paths_hbm<D, EXACT, true>(csr, dist, aux, s, t, visited, stack,
@@ -1281,8 +1261,6 @@ hipError_t ksp2_launch(const ogs_graph& g, const ogs_unit* sources,
                      (opts().kspWaveTrace ? 1 : 0) | (opts().kspPrune ? 2 : 0));
   return hipGetLastError();
 }
-
-hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
 
 // "ksp_queue": 1 (default) workgroup units solve SPF with LDS node lists,
 // 0 with the pull fixpoint. "ksp_stage": -1 (default) auto -- the edges in

@@ -19,6 +19,7 @@
 
 #include "openr_gpu.h"
 #include "spf_core.h"
+#include "launch.h"
 
 namespace ogs {
 

@@ -39,6 +39,7 @@
 #include "spf_lds.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -147,23 +148,6 @@ __global__ __launch_bounds__(kBlock) void route_stream_kernel(
 // profiles/r03_store_pattern.log, r03_store_nt_ab.log.
 // EngineOptions::routeStoreNt (engine.h), default 2
 
-bool try_ms(const ogs_graph& g, const ogs_prefix_table& pt, int hasPrefixes,
-            const ogs_unit* units, int nUnits, uint32_t flags, int W,
-            const ogs_spf_out& out, hipStream_t stream, hipError_t* err);
-bool frontier_fits(const ogs_graph& g, uint32_t flags, int W);
-size_t chunk_scratch_bytes(const ogs_graph& g);
-size_t desc_scratch_bytes(const ogs_graph& g);
-hipError_t launch_frontier_spf(const ogs_graph& g, const ogs_unit* units,
-                               int nUnits, uint32_t flags, int W,
-                               uint32_t* dist, uint32_t* nh, void* scratch,
-                               hipStream_t stream);
-hipError_t launch_frontier_routes(const ogs_graph& g, const ogs_prefix_table& pt,
-                                  const uint32_t* key, const ogs_unit* units,
-                                  int nUnits, uint32_t flags, int W,
-                                  const ogs_spf_out& out, void* scratch,
-                                  hipStream_t stream);
-void stream_parts(int nUnits, int W, int P, int* parts);
-
 template <int W>
 hipError_t launch_route_stream(const ogs_graph& g, const ogs_prefix_table& pt,
                                const uint32_t* key, const ogs_unit* units,
@@ -171,20 +155,11 @@ hipError_t launch_route_stream(const ogs_graph& g, const ogs_prefix_table& pt,
                                const uint32_t* nh, const ogs_spf_out& out,
                                hipStream_t stream, int parts = 1) {
   const size_t lds = size_t(g.max_nodes) * (2 + W) * 4;
-  auto k = route_stream_kernel<W>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(lds));
-    if (e != hipSuccess) return e;
-  }
   if (opts().routeStoreNt & 1) flags |= kFlagNtStores;
-  hipLaunchKernelGGL(k, dim3(unsigned(nUnits) * unsigned(parts)), dim3(kBlock), lds, stream, g,
-                     pt, key, units, flags, dist, nh, out, uint32_t(parts));
-  return hipGetLastError();
+  return launch_dyn_lds(route_stream_kernel<W>, dim3(unsigned(nUnits) * unsigned(parts)),
+                        dim3(kBlock), lds, stream, g, pt, key, units, flags, dist, nh, out,
+                        uint32_t(parts));
 }
-
-static size_t round256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // SPF only through the frontier kernel (callers without a prefix table).
 bool try_frontier(const ogs_graph& g, const ogs_unit* units, int nUnits,
@@ -198,14 +173,6 @@ bool try_frontier(const ogs_graph& g, const ogs_unit* units, int nUnits,
   *err = launch_frontier_spf(g, units, nUnits, flags, W, dist, nh, ws, stream);
   return true;
 }
-
-hipError_t launch_frontier_variants(const ogs_graph& g, const ogs_prefix_table& pt,
-                                    const uint32_t* key, const ogs_unit* units,
-                                    int n, uint32_t flags, int W,
-                                    const ogs_spf_out& out,
-                                    const ogs_unit_mods* mods,
-                                    ogs_route_diff* diff, void* scratch,
-                                    hipStream_t stream);
 
 // ogs_spf_routes_variants: key fold + zeroed diff bitmap + fused frontier
 // SPF / RouteDb / diff launch. *unsupported when outside the frontier path.
@@ -328,13 +295,6 @@ bool try_ms_stream(const ogs_graph& g, const ogs_prefix_table& pt,
   }
   return true;
 }
-
-
-hipError_t launch_spf_routes(const ogs_graph& g, const ogs_prefix_table* pt,
-                             const ogs_unit* units, int nUnits, uint32_t flags, int W,
-                             const ogs_spf_out& out, hipStream_t stream, int* unsupported);
-int small_unit_width();
-bool use_global(const ogs_graph& g, int W, uint32_t flags);
 
 // ogs_spf_routes_groups: every group's RouteDbs over one graph / prefix
 // table. With route_stream 5 on a large shared topology whose image fits

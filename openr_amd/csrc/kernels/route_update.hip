@@ -21,6 +21,7 @@
 
 #include "openr_gpu.h"
 #include "spf_core.h"
+#include "launch.h"
 
 namespace ogs {
 

@@ -50,6 +50,34 @@ struct UnitScope<kBlock> {  // one workgroup per unit
   }
 };
 
+// A unit's state in HBM (spf_global.hip, ksp.hip): the unit's workgroup runs
+// on one CU, so the state stays in that XCD's L2 for the whole launch.
+// L2SYNC: a round ends with every wave's stores drained and a barrier, and
+// state written in this launch is read back through sc1 (L2-served,
+// L1-bypassing) loads -- the L1 may hold lines that L2 atomics have since
+// changed (MI355X_MICROARCH.md, inter-workgroup visibility). Else:
+// agent-scope release / acquire fences around the barrier and plain loads.
+template <bool L2SYNC>
+__device__ __forceinline__ void round_sync() {
+  if constexpr (L2SYNC) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  }
+}
+
+template <bool L2SYNC, typename T>
+__device__ __forceinline__ T ld_state(const T* p) {
+  if constexpr (L2SYNC) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    return *p;
+  }
+}
+
 __device__ __forceinline__ uint32_t edge_dst(uint32_t lo) {
   return lo & OGS_EDGE_DST_MASK;
 }

@@ -35,6 +35,7 @@
 #include "route_core.h"
 #include "route_global.h"
 #include "spf_core.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -391,17 +392,14 @@ __global__ __launch_bounds__(64) void spf_exact_wide_kernel(
   }
 }
 
-hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
-
 hipError_t launch_exact_wide(const ogs_graph& g, const ogs_prefix_table* pt,
                              const ogs_unit* units, int nUnits, uint32_t flags, int W,
                              const ogs_spf_out& out, hipStream_t stream) {
   const size_t Sn = size_t(g.max_nodes), U = size_t(nUnits);
-  auto r256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t distBytes = out.dist ? 0 : r256(U * Sn * 8);
-  const size_t nhBytes = out.nh ? 0 : r256(U * W * Sn * 4);
-  const size_t scratchBytes = r256(U * 2 * Sn * 4);
-  const size_t reachBytes = out.reached ? 0 : r256(U * ((Sn + 31) / 32) * 4);
+  const size_t distBytes = out.dist ? 0 : round256(U * Sn * 8);
+  const size_t nhBytes = out.nh ? 0 : round256(U * W * Sn * 4);
+  const size_t scratchBytes = round256(U * 2 * Sn * 4);
+  const size_t reachBytes = out.reached ? 0 : round256(U * ((Sn + 31) / 32) * 4);
   void* ws = nullptr;
   hipError_t e = workspace(distBytes + nhBytes + scratchBytes + reachBytes, stream, &ws);
   if (e != hipSuccess) return e;
@@ -434,11 +432,10 @@ hipError_t launch_exact_w(const ogs_graph& g, const ogs_prefix_table* pt,
                           const ogs_unit* units, int nUnits, uint32_t flags,
                           const ogs_spf_out& out, hipStream_t stream) {
   const size_t Sn = size_t(g.max_nodes), U = size_t(nUnits);
-  auto r256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t distBytes = out.dist ? 0 : r256(U * Sn * 8);
-  const size_t nhBytes = out.nh ? 0 : r256(U * W * Sn * 4);
-  const size_t scratchBytes = r256(U * 2 * Sn * 4);
-  const size_t reachBytes = out.reached ? 0 : r256(U * ((Sn + 31) / 32) * 4);
+  const size_t distBytes = out.dist ? 0 : round256(U * Sn * 8);
+  const size_t nhBytes = out.nh ? 0 : round256(U * W * Sn * 4);
+  const size_t scratchBytes = round256(U * 2 * Sn * 4);
+  const size_t reachBytes = out.reached ? 0 : round256(U * ((Sn + 31) / 32) * 4);
   void* ws = nullptr;
   hipError_t e = workspace(distBytes + nhBytes + scratchBytes + reachBytes, stream, &ws);
   if (e != hipSuccess) return e;

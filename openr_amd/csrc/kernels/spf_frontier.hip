@@ -38,6 +38,7 @@
 #include "route_stream.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -766,8 +767,7 @@ __device__ __forceinline__ void queue_spf_packed(
 #endif
 }
 
-uint32_t frontier_lds_bytes(uint32_t Sn, int W, bool queue = false, bool ninfo = true,
-                            bool stamp8 = false) {
+uint32_t frontier_lds_bytes(uint32_t Sn, int W, bool queue, bool ninfo, bool stamp8) {
   const uint32_t core = 4u * (((Sn + 3u) & ~3u) + ((Sn * W + 3u) & ~3u));
   if (!queue) return core + (stamp8 ? ((Sn + 3u) & ~3u) : 2u * ((Sn + 1u) & ~1u));
   // + u32 stamps + two u16 node lists (+ u32 node info [Sn + 1])
@@ -1022,17 +1022,10 @@ hipError_t launch_frontier_q(const ogs_graph& g, const ogs_prefix_table& pt,
   if (opts().spfLaneWalk == 0 || (opts().spfLaneWalk < 0 && B < 512)) flags |= kFlagSlotWalk;
   if (!opts().spfPreload) flags |= kFlagNoPreload;
   if (opts().routeStoreNt & 1) flags |= kFlagNtStores;
-  auto k = spf_frontier_kernel<W, ROUTES, MODS, DIFF, QMODE, OUTS3, B>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(lds));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(unsigned(nUnits) * unsigned(parts)), dim3(B), lds, stream, g, pt,
-                     key, chunks, nChunk, chunk_cap(g), units, flags, dist, nh, out, mods,
-                     diff, uint32_t(parts));
-  return hipGetLastError();
+  return launch_dyn_lds(spf_frontier_kernel<W, ROUTES, MODS, DIFF, QMODE, OUTS3, B>,
+                        dim3(unsigned(nUnits) * unsigned(parts)), dim3(B), lds, stream, g, pt,
+                        key, chunks, nChunk, chunk_cap(g), units, flags, dist, nh, out, mods,
+                        diff, uint32_t(parts));
 }
 
 // Geometry of an all-sources RouteDb launch (OUTS3): threads per workgroup

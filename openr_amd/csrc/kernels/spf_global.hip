@@ -6,20 +6,31 @@
 // LinkState.cpp:720-820; distances are the least solution of dist(v) = min
 // over usable u of dist(u) + w(u, v), next-hop sets the least solution of
 // NH(v) = U over tight u of (u == src ? {slot} : NH(u)), u relaxing iff u is
-// the source or not hard-drained, 741-752). What differs is where the unit's
-// state lives: dist / next-hop sets / push stamps / the two frontier lists
-// are in HBM (the caller's output rows or the workspace), so there is no
-// size limit but the 21-bit node ids of the edge encoding. One workgroup of
-// 1024 threads per unit walks the frontier list of the round; relaxations
-// are L2 atomics (atomicMin / atomicOr). A unit's workgroup runs on ONE CU,
-// so its state never leaves that XCD's L2 until the kernel ends: a round
-// ends with every wave's stores drained (s_waitcnt vmcnt(0)) and a workgroup
-// barrier, and every read of state written in this launch is an L2-served
-// `sc1` load (L1 bypassed: MI355X_MICROARCH.md, inter-workgroup visibility
-// table) -- no L2 write-back / L1 invalidate per round. (The first form
-// used agent-scope release + acquire fences per round, ~3.5 us of cache
-// maintenance each: option "spf_global_sync" 0 keeps it for A/B.) Every
-// round touches only the rows of the nodes changed in the previous round.
+// the source or not hard-drained, 741-752). One workgroup of 1024 threads per
+// unit walks the frontier list of the round, so every round touches only the
+// rows of the nodes changed in the previous round; the two lists are rows in
+// HBM, so there is no size limit but the 21-bit node ids of the edge
+// encoding.
+//
+// spf_global_kernel is the two-phase form, stated once: a dist phase, then
+// a next-hop phase seeded from the source's row. A state policy says where
+// the unit's distances and next-hop words live and how "already in the next
+// list" is remembered:
+//   HbmState      all in HBM (the caller's output rows or the workspace),
+//                 relaxations are L2 atomics, an HBM stamp row; any size, and
+//                 any next-hop width (W == kWRuntime: a runtime word count)
+//   LdsDistState  distances in LDS, next-hop words in HBM, parity bitsets
+//   LdsBothState  distances and next-hop words in LDS, a per-round bitset
+// spf_global_lds3_kernel is the one-phase form (packed {dist, nh} words in
+// LDS, W = 1, u32 distances).
+//
+// A unit's workgroup runs on ONE CU, so its HBM state never leaves that
+// XCD's L2 until the kernel ends: a round ends with every wave's stores
+// drained and a workgroup barrier, and every read of state written in this
+// launch is an L2-served `sc1` load (spf_core.h, round_sync / ld_state) -- no
+// L2 write-back / L1 invalidate per round. (The first form used agent-scope
+// release + acquire fences per round, ~3.5 us of cache maintenance each:
+// option "spf_global_sync" 0 keeps it for A/B.)
 //
 // Routes: route_global.h, one thread per (unit, prefix) against the unit's
 // state in HBM. u32 or u64 distances (OGS_F_WIDE_METRIC).
@@ -32,716 +43,450 @@
 #include "route_global.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
 constexpr int kGBlock = 1024;
-constexpr int kGRow = 4;  // row edges per step of a frontier node
+constexpr int kGRow = 4;      // row edges per step of a frontier node
+constexpr int kWRuntime = 0;  // W: the next-hop word count is a kernel argument
 
-// L2SYNC: stores drained + barrier (state read back through sc1 loads);
-// else agent-scope release / acquire fences around the barrier.
-template <bool L2SYNC>
-__device__ __forceinline__ void round_sync() {
-  if constexpr (L2SYNC) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  }
-}
-
-// Read of state written earlier in this launch: an sc1 (L2-served) load
-// under L2SYNC, a plain load after the agent acquire otherwise.
-template <bool L2SYNC, typename T>
-__device__ __forceinline__ T ld_state(const T* p) {
-  if constexpr (L2SYNC) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    return *p;
-  }
-}
-
+// ---- the unit: its source and its topology's CSR ---------------------------
 template <typename D>
-__device__ __forceinline__ D atomic_min_d(D* p, D v) {
-  return atomicMin(p, v);
-}
+struct GUnit {
+  uint32_t u0, s, N;
+  size_t Sn;
+  const uint32_t* gRow;
+  uint32_t e0;
+  const uint64_t* edges;  // edges[gRow[v] - e0 ...]: v's row
+  const uint8_t* nflags;
+  bool hop;
 
-// One unit's SPF into HBM. dist[v] (D), nh[w * Sn + v], stamp/q0/q1 scratch
-// rows of this unit (>= N entries each).
-template <typename D, int W, bool L2SYNC>
-__global__ __launch_bounds__(kGBlock) void spf_global_kernel(
-    ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags,
-    D* __restrict__ oDist, uint32_t* __restrict__ oNh, uint32_t* __restrict__ scratch) {
-  constexpr D kInf = DistInf<D>::value;
-  const int tid = threadIdx.x;
-  const uint32_t u0 = blockIdx.x;
-  const ogs_unit unit = units[u0];
-  const uint32_t s = unit.src;
-  const uint32_t nb = g.node_base[unit.topo];
-  const uint32_t N = g.node_base[unit.topo + 1] - nb;
-  const size_t Sn = size_t(g.max_nodes);
-  const uint32_t* __restrict__ gRow = g.row_ptr + nb;
-  const uint32_t e0 = gRow[0];
-  const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* __restrict__ nflags = g.node_flags + nb;
-  const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
-  D* dist = oDist + u0 * Sn;
-  uint32_t* nh = oNh + u0 * W * Sn;
-  uint32_t* stamp = scratch + u0 * 3 * Sn;
-  uint32_t* q0 = stamp + Sn;
-  uint32_t* q1 = q0 + Sn;
-  __shared__ uint32_t qcnt[3];
-
-  for (uint32_t v = tid; v < N; v += kGBlock) {
-    dist[v] = (v == s) ? D(0) : kInf;
-    stamp[v] = 0u;
-#pragma unroll
-    for (int w = 0; w < W; ++w) nh[w * Sn + v] = 0u;
+  __device__ __forceinline__ GUnit(const ogs_graph& g, const ogs_unit& unit, uint32_t flags)
+      : u0(blockIdx.x), s(unit.src), Sn(size_t(g.max_nodes)),
+        hop((flags & OGS_F_HOP_METRIC) != 0) {
+    const uint32_t nb = g.node_base[unit.topo];
+    N = g.node_base[unit.topo + 1] - nb;
+    gRow = g.row_ptr + nb;
+    e0 = gRow[0];
+    edges = g.edges + e0;
+    nflags = g.node_flags + nb;
   }
-  if (tid == 0) {
-    q1[0] = s;  // round 1's list: buffer r & 1, count slot r % 3
-    qcnt[0] = 0u;
-    qcnt[1] = 1u;
-    qcnt[2] = 0u;
-  }
-  round_sync<L2SYNC>();
-  // t's first push of round r + 1 (stamp claimed): append to that list
-  auto push = [&](uint32_t t, uint32_t r) {
-    const uint32_t at = atomicAdd(&qcnt[(r + 1) % 3], 1u);
-    ((r + 1) & 1 ? q1 : q0)[at] = t;
-  };
-  auto append = [&](uint32_t t, uint32_t r) {
-    if (atomicMax(&stamp[t], r + 1) < r + 1) push(t, r);
-  };
-  auto weight = [&](uint64_t x) -> D {
+  __device__ __forceinline__ D weight(uint64_t x) const {
     return hop ? D(1) : D(static_cast<uint32_t>(x >> 32));
-  };
+  }
+  // a hard-drained node relaxes nothing unless it is the source (741-752)
+  __device__ __forceinline__ bool drained(uint32_t v) const {
+    return nflags[v] & OGS_NODE_OVERLOADED;
+  }
+};
 
-  // ---- dist phase: rows of the nodes whose distance dropped last round ----
-  uint32_t r = 1, n = 1;
-  for (; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<L2SYNC>(cur + i);
-      if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
-      const D dv = ld_state<L2SYNC>(dist + v);
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      // kGRow edges at a time, each step's memory operations independent
-      // (edge words, then the targets' dist, then the atomicMins, then the
-      // stamps): one L2 round trip per step instead of one per edge and step
-      for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
-        uint32_t t[kGRow];
-        D c[kGRow], seen[kGRow];
-        bool ok[kGRow];
+// kB edges of a row from edge e on (`left` remain), decoded: target, whether
+// the link is up, and the candidate distance dv + w
+template <typename D, int kB>
+struct GEdges {
+  uint32_t t[kB];
+  D c[kB];
+  bool up[kB];
+  __device__ __forceinline__ GEdges(const GUnit<D>& u, D dv, uint32_t e, uint32_t left) {
 #pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          const uint64_t x = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
-          const uint32_t lo = static_cast<uint32_t>(x);
-          ok[k] = !(lo & OGS_EDGE_DOWN);
-          t[k] = edge_dst(lo);
-          c[k] = dv + weight(x);
-        }
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) seen[k] = ok[k] ? ld_state<L2SYNC>(dist + t[k]) : D(0);
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          ok[k] = ok[k] && c[k] < seen[k];
-          seen[k] = ok[k] ? atomic_min_d(&dist[t[k]], c[k]) : D(0);
-        }
-        uint32_t st[kGRow];
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          ok[k] = ok[k] && c[k] < seen[k];
-          st[k] = ok[k] ? atomicMax(&stamp[t[k]], r + 1) : r + 1;
-        }
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          if (ok[k] && st[k] < r + 1) push(t[k], r);
-        }
-      }
+    for (int k = 0; k < kB; ++k) {
+      const uint64_t x = uint32_t(k) < left ? u.edges[e + k] : uint64_t(OGS_EDGE_DOWN);
+      const uint32_t lo = static_cast<uint32_t>(x);
+      up[k] = !(lo & OGS_EDGE_DOWN);
+      t[k] = edge_dst(lo);
+      c[k] = dv + u.weight(x);
     }
+  }
+};
+
+// ---- the frontier lists: two HBM rows, round r's list in row r & 1 with its
+// length in count slot r % 3 (LDS) -------------------------------------------
+struct GLists {
+  uint32_t* q;  // [2 * Sn]
+  size_t Sn;
+  uint32_t* qcnt;
+
+  __device__ __forceinline__ void init(uint32_t s) {  // round 1's list: the source
+    if (threadIdx.x == 0) {
+      q[Sn] = s;
+      qcnt[0] = 0u;
+      qcnt[1] = 1u;
+      qcnt[2] = 0u;
+    }
+  }
+  __device__ __forceinline__ uint32_t* list(uint32_t r) const { return q + (r & 1) * Sn; }
+  __device__ __forceinline__ void begin_round(uint32_t r) {
+    if (threadIdx.x == 0) qcnt[(r + 2) % 3] = 0u;
+  }
+  __device__ __forceinline__ void push(uint32_t t, uint32_t r) {  // into round r + 1's list
+    const uint32_t at = atomicAdd(&qcnt[(r + 1) % 3], 1u);
+    list(r + 1)[at] = t;
+  }
+  // the length of round r + 1's list, once round r's pushes are visible
+  template <bool L2SYNC>
+  __device__ __forceinline__ uint32_t end_round(uint32_t r) {
     round_sync<L2SYNC>();
-    n = qcnt[(r + 1) % 3];
+    const uint32_t n = qcnt[(r + 1) % 3];
     __syncthreads();  // every thread has read the count before it is reset
+    return n;
   }
+  __device__ __forceinline__ void reset() {  // between the phases
+    if (threadIdx.x == 0) qcnt[0] = qcnt[1] = qcnt[2] = 0u;
+  }
+};
 
-  // ---- next-hop phase: the source's row seeds link slots, tight pushes ----
-  const uint32_t r0 = r;
-  if (tid == 0) qcnt[0] = qcnt[1] = qcnt[2] = 0u;
-  round_sync<L2SYNC>();
-  {
-    const uint32_t b = gRow[s] - e0, m = gRow[s + 1] - e0 - b;
-    for (uint32_t j = tid; j < m && j < 32u * W; j += kGBlock) {
-      const uint64_t x = edges[b + j];
-      const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      const uint32_t t = edge_dst(lo);
-      if (weight(x) == ld_state<L2SYNC>(dist + t)) {
-        atomicOr(&nh[(j >> 5) * Sn + t], 1u << (j & 31u));
-        append(t, r0);
-      }
-    }
+// ---- "t is already in the next list": first_push(t, r) is true for t's
+// first push of round r + 1 ---------------------------------------------------
+// An HBM row of the last round each node was pushed for (rounds count on
+// through both phases, so the row is never cleared).
+struct StampMember {
+  static constexpr bool kPerRound = false;
+  uint32_t* stamp;
+  __device__ __forceinline__ void init(uint32_t N) {
+    for (uint32_t v = threadIdx.x; v < N; v += kGBlock) stamp[v] = 0u;
   }
-  round_sync<L2SYNC>();
-  n = qcnt[(r0 + 1) % 3];
-  __syncthreads();
-  for (r = r0 + 1; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<L2SYNC>(cur + i);
-      if (v == s || (nflags[v] & OGS_NODE_OVERLOADED)) continue;
-      const D dv = ld_state<L2SYNC>(dist + v);
-      uint32_t nv[W];
-#pragma unroll
-      for (int w = 0; w < W; ++w) nv[w] = ld_state<L2SYNC>(nh + w * Sn + v);
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      constexpr int kB = W <= 4 ? kGRow : 2;  // edges per step (as above)
-      for (uint32_t j0 = 0; j0 < m; j0 += kB) {
-        uint32_t t[kB];
-        bool ok[kB];
-        D c[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          const uint64_t x = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
-          const uint32_t lo = static_cast<uint32_t>(x);
-          ok[k] = !(lo & OGS_EDGE_DOWN);
-          t[k] = edge_dst(lo);
-          c[k] = dv + weight(x);
-        }
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          ok[k] = ok[k] && c[k] == ld_state<L2SYNC>(dist + t[k]);  // tight
-        }
-        uint32_t a[kB][W];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-#pragma unroll
-          for (int w = 0; w < W; ++w) {
-            a[k][w] = ok[k] ? nv[w] & ~ld_state<L2SYNC>(nh + w * Sn + t[k]) : 0u;
-          }
-        }
-        bool add[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          add[k] = false;
-#pragma unroll
-          for (int w = 0; w < W; ++w) {
-            if (a[k][w] && (a[k][w] & ~atomicOr(&nh[w * Sn + t[k]], a[k][w]))) add[k] = true;
-          }
-        }
-        uint32_t st[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) st[k] = add[k] ? atomicMax(&stamp[t[k]], r + 1) : r + 1;
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          if (add[k] && st[k] < r + 1) push(t[k], r);
-        }
-      }
-    }
-    round_sync<L2SYNC>();
-    n = qcnt[(r + 1) % 3];
+  __device__ __forceinline__ bool first_push(uint32_t t, uint32_t r) {
+    return atomicMax(&stamp[t], r + 1) < r + 1;
+  }
+  __device__ __forceinline__ void consume(uint32_t, uint32_t) {}
+  __device__ __forceinline__ void reset() {}
+};
+
+// A bitset per round parity in LDS: bit set on the first push of a round,
+// cleared when the entry is consumed (round 1's entry was never pushed).
+struct ParityMember {
+  static constexpr bool kPerRound = false;
+  uint32_t* mark;  // [2 * mw]
+  uint32_t mw;
+  __device__ __forceinline__ void init(uint32_t) { reset(); }
+  __device__ __forceinline__ bool first_push(uint32_t t, uint32_t r) {
+    const uint32_t bit = 1u << (t & 31u);
+    return !(atomicOr(&mark[((r + 1) & 1) * mw + (t >> 5)], bit) & bit);
+  }
+  __device__ __forceinline__ void consume(uint32_t v, uint32_t r) {
+    if (r > 1) atomicAnd(&mark[(r & 1) * mw + (v >> 5)], ~(1u << (v & 31u)));
+  }
+  // a phase's last round consumed nothing: clear both parities
+  __device__ __forceinline__ void reset() {
+    for (uint32_t i = threadIdx.x; i < 2 * mw; i += kGBlock) mark[i] = 0u;
+  }
+};
+
+// ONE bitset in LDS, cleared in bulk at the start of every round -- behind
+// the same barrier that the round's first frontier loads are already in
+// flight across.
+struct RoundMember {
+  static constexpr bool kPerRound = true;
+  uint32_t* mark;  // [mw]
+  uint32_t mw;
+  __device__ __forceinline__ void init(uint32_t) {}
+  __device__ __forceinline__ bool first_push(uint32_t t, uint32_t) {
+    const uint32_t bit = 1u << (t & 31u);
+    return !(atomicOr(&mark[t >> 5], bit) & bit);
+  }
+  __device__ __forceinline__ void begin_round() {
+    reset();
     __syncthreads();
   }
-}
-
-// ---- next-hop sets of any width (sources of more than 512 links): the
-// all-HBM form with a runtime word count; rslot is never read (push-style
-// relaxation, link slots from the source's own row) ---------------------
-template <typename D>
-__global__ __launch_bounds__(kGBlock) void spf_global_wide_kernel(
-    ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags, int W,
-    D* __restrict__ oDist, uint32_t* __restrict__ oNh, uint32_t* __restrict__ scratch) {
-  constexpr D kInf = DistInf<D>::value;
-  const int tid = threadIdx.x;
-  const uint32_t u0 = blockIdx.x;
-  const ogs_unit unit = units[u0];
-  const uint32_t s = unit.src;
-  const uint32_t nb = g.node_base[unit.topo];
-  const uint32_t N = g.node_base[unit.topo + 1] - nb;
-  const size_t Sn = size_t(g.max_nodes);
-  const uint32_t* __restrict__ gRow = g.row_ptr + nb;
-  const uint32_t e0 = gRow[0];
-  const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* __restrict__ nflags = g.node_flags + nb;
-  const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
-  D* dist = oDist + u0 * Sn;
-  uint32_t* nh = oNh + u0 * size_t(W) * Sn;
-  uint32_t* stamp = scratch + u0 * 3 * Sn;
-  uint32_t* q0 = stamp + Sn;
-  uint32_t* q1 = q0 + Sn;
-  __shared__ uint32_t qcnt[3];
-
-  for (uint32_t v = tid; v < N; v += kGBlock) {
-    dist[v] = (v == s) ? D(0) : kInf;
-    stamp[v] = 0u;
-    for (int w = 0; w < W; ++w) nh[w * Sn + v] = 0u;
+  __device__ __forceinline__ void consume(uint32_t, uint32_t) {}
+  __device__ __forceinline__ void reset() {
+    for (uint32_t i = threadIdx.x; i < mw; i += kGBlock) mark[i] = 0u;
   }
-  if (tid == 0) {
-    q1[0] = s;
-    qcnt[0] = 0u;
-    qcnt[1] = 1u;
-    qcnt[2] = 0u;
-  }
-  round_sync<true>();
-  auto push = [&](uint32_t t, uint32_t r) {
-    const uint32_t at = atomicAdd(&qcnt[(r + 1) % 3], 1u);
-    ((r + 1) & 1 ? q1 : q0)[at] = t;
-  };
-  auto append = [&](uint32_t t, uint32_t r) {
-    if (atomicMax(&stamp[t], r + 1) < r + 1) push(t, r);
-  };
-  auto weight = [&](uint64_t x) -> D {
-    return hop ? D(1) : D(static_cast<uint32_t>(x >> 32));
-  };
-  // ---- dist phase ----------------------------------------------------------
-  uint32_t r = 1, n = 1;
-  for (; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<true>(cur + i);
-      if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
-      const D dv = ld_state<true>(dist + v);
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      for (uint32_t j = 0; j < m; ++j) {
-        const uint64_t x = edges[b + j];
-        const uint32_t lo = static_cast<uint32_t>(x);
-        if (lo & OGS_EDGE_DOWN) continue;
-        const uint32_t t = edge_dst(lo);
-        const D c = dv + weight(x);
-        if (c < ld_state<true>(dist + t) && c < atomic_min_d(&dist[t], c)) append(t, r);
-      }
-    }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
-  // ---- next-hop phase ------------------------------------------------------
-  const uint32_t r0 = r;
-  if (tid == 0) qcnt[0] = qcnt[1] = qcnt[2] = 0u;
-  round_sync<true>();
-  {
-    const uint32_t b = gRow[s] - e0, m = gRow[s + 1] - e0 - b;
-    for (uint32_t j = tid; j < m && j < 32u * uint32_t(W); j += kGBlock) {
-      const uint64_t x = edges[b + j];
-      const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      const uint32_t t = edge_dst(lo);
-      if (weight(x) == ld_state<true>(dist + t)) {
-        atomicOr(&nh[(j >> 5) * Sn + t], 1u << (j & 31u));
-        append(t, r0);
-      }
-    }
-  }
-  round_sync<true>();
-  n = qcnt[(r0 + 1) % 3];
-  __syncthreads();
-  for (r = r0 + 1; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<true>(cur + i);
-      if (v == s || (nflags[v] & OGS_NODE_OVERLOADED)) continue;
-      const D dv = ld_state<true>(dist + v);
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      for (uint32_t j = 0; j < m; ++j) {
-        const uint64_t x = edges[b + j];
-        const uint32_t lo = static_cast<uint32_t>(x);
-        if (lo & OGS_EDGE_DOWN) continue;
-        const uint32_t t = edge_dst(lo);
-        if (dv + weight(x) != ld_state<true>(dist + t)) continue;  // not tight
-        bool add = false;
-        for (int w = 0; w < W; ++w) {
-          const uint32_t a = ld_state<true>(nh + w * Sn + v) & ~ld_state<true>(nh + w * Sn + t);
-          if (a && (a & ~atomicOr(&nh[w * Sn + t], a))) add = true;
-        }
-        if (add) append(t, r);
-      }
-    }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
-}
+};
 
-// SPF (+ RouteDb) with next-hop sets wider than 16 words.
-hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
+// ---- where dist[v] (D) and nh[w * Sn + v] live -------------------------------
+// kStaged: a relaxation step's memory operations are issued class by class
+// over the step's edges (they are L2 round trips), else edge by edge (LDS).
+// Both in HBM. L2SYNC: spf_core.h.
+template <typename D, int W, bool L2SYNC>
+struct HbmState {
+  using Dist = D;
+  using Member = StampMember;
+  static constexpr int kW = W;
+  static constexpr bool kL2Sync = L2SYNC, kDistStaged = true, kNhStaged = W != kWRuntime;
+  static constexpr int kNhStep = W == kWRuntime ? 1 : W <= 4 ? kGRow : 2;
+  D* dist;
+  uint32_t* nh;
+  size_t Sn;
+  int wn;
 
-template <typename D>
-hipError_t launch_global_wide(const ogs_graph& g, const ogs_prefix_table* pt,
-                              const ogs_unit* units, int nUnits, uint32_t flags, int W,
-                              const ogs_spf_out& out, hipStream_t stream) {
-  const size_t Sn = size_t(g.max_nodes), U = size_t(nUnits);
-  auto r256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t distBytes = out.dist ? 0 : r256(U * Sn * sizeof(D));
-  const size_t nhBytes = out.nh ? 0 : r256(U * W * Sn * 4);
-  const size_t scratchBytes = r256(U * 3 * Sn * 4);
-  void* ws = nullptr;
-  hipError_t e = workspace(distBytes + nhBytes + scratchBytes, stream, &ws);
-  if (e != hipSuccess) return e;
-  char* base = static_cast<char*>(ws);
-  D* dist = out.dist ? static_cast<D*>(out.dist) : reinterpret_cast<D*>(base);
-  uint32_t* nh = out.nh ? out.nh : reinterpret_cast<uint32_t*>(base + distBytes);
-  uint32_t* scratch = reinterpret_cast<uint32_t*>(base + distBytes + nhBytes);
-  hipLaunchKernelGGL((spf_global_wide_kernel<D>), dim3(nUnits), dim3(kGBlock), 0, stream, g,
-                     units, flags, W, dist, nh, scratch);
-  e = hipGetLastError();
-  if (e != hipSuccess || !pt || pt->max_prefixes == 0) return e;
-  return launch_route_global_wide<D>(g, *pt, units, nUnits, flags, W, dist, nh, out, stream);
-}
-
-hipError_t launch_spf_routes_global_wide(const ogs_graph& g, const ogs_prefix_table* pt,
-                                         const ogs_unit* units, int nUnits, uint32_t flags,
-                                         int W, const ogs_spf_out& out, hipStream_t stream) {
-  if (flags & OGS_F_WIDE_METRIC) {
-    return launch_global_wide<uint64_t>(g, pt, units, nUnits, flags, W, out, stream);
+  __device__ __forceinline__ HbmState(const GUnit<D>& u, int Wn, D* oDist, uint32_t* oNh, char*)
+      : dist(oDist + u.u0 * u.Sn), Sn(u.Sn), wn(W == kWRuntime ? Wn : W) {
+    nh = oNh + size_t(u.u0) * wn * Sn;
   }
-  return launch_global_wide<uint32_t>(g, pt, units, nUnits, flags, W, out, stream);
-}
+  __device__ __forceinline__ Member member(uint32_t* stampRow) const { return Member{stampRow}; }
+  __device__ __forceinline__ int words() const { return W == kWRuntime ? wn : W; }
+  __device__ __forceinline__ D ld_dist(uint32_t v) const { return ld_state<L2SYNC>(dist + v); }
+  __device__ __forceinline__ D min_dist(uint32_t t, D c) { return atomicMin(&dist[t], c); }
+  __device__ __forceinline__ uint32_t ld_nh(int w, uint32_t v) const {
+    return ld_state<L2SYNC>(nh + w * Sn + v);
+  }
+  __device__ __forceinline__ uint32_t* nh_word(int w, uint32_t v) { return nh + w * Sn + v; }
+  __device__ __forceinline__ void after_dist(const GUnit<D>&) {}
+  __device__ __forceinline__ void after_nh(const GUnit<D>&) {}
+};
 
-// ---- dist in LDS (units whose distances fit: N * sizeof(D) + two list
-// bitsets <= 160 kB, e.g. 20k nodes at u32) ----------------------------------
-// The same rounds with the unit's distances in LDS: a dist round's chain is
-// then frontier entry -> row -> edge words (L2) with LDS atomics for the
-// relaxations, instead of dist loads and atomics whose lines the atomics
-// drop from L2. List membership is a bitset per round parity in LDS (bit set
-// on the first push of a round, cleared when the entry is consumed). The
-// next-hop words stay in HBM; the final distances are copied to the caller's
-// row for the route kernel.
+// Distances in LDS (N * sizeof(D) + two list bitsets <= 160 kB, e.g. 20k
+// nodes at u32): a dist round's chain is frontier entry -> row -> edge words
+// (L2) with LDS atomics for the relaxations, instead of dist loads and
+// atomics whose lines the atomics drop from L2. The next-hop words stay in
+// HBM; the final distances are copied to the caller's row for the route
+// kernel.
 uint32_t global_lds_bytes(uint32_t Sn, uint32_t dsize) {
   return ((Sn * dsize + 15u) & ~15u) + 2u * 4u * ((Sn + 31u) / 32u);
 }
 
 template <typename D, int W>
-__global__ __launch_bounds__(kGBlock) void spf_global_lds_kernel(
-    ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags,
-    D* __restrict__ oDist, uint32_t* __restrict__ oNh, uint32_t* __restrict__ scratch) {
-  constexpr D kInf = DistInf<D>::value;
-  const int tid = threadIdx.x;
-  const uint32_t u0 = blockIdx.x;
-  const ogs_unit unit = units[u0];
-  const uint32_t s = unit.src;
-  const uint32_t nb = g.node_base[unit.topo];
-  const uint32_t N = g.node_base[unit.topo + 1] - nb;
-  const size_t Sn = size_t(g.max_nodes);
-  const uint32_t* __restrict__ gRow = g.row_ptr + nb;
-  const uint32_t e0 = gRow[0];
-  const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* __restrict__ nflags = g.node_flags + nb;
-  const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
-  uint32_t* nh = oNh + u0 * W * Sn;
-  uint32_t* q0 = scratch + u0 * 3 * Sn + Sn;  // the HBM form's list rows
-  uint32_t* q1 = q0 + Sn;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  D* dist = reinterpret_cast<D*>(smem);
-  const uint32_t mw = (uint32_t(Sn) + 31u) / 32u;
-  uint32_t* mark = reinterpret_cast<uint32_t*>(smem + ((Sn * sizeof(D) + 15u) & ~size_t(15)));
-  __shared__ uint32_t qcnt[3];
+struct LdsDistState {
+  using Dist = D;
+  using Member = ParityMember;
+  static constexpr int kW = W;
+  static constexpr bool kL2Sync = true, kDistStaged = false, kNhStaged = true;
+  static constexpr int kNhStep = W <= 4 ? kGRow : 2;
+  D* dist;         // LDS
+  uint32_t* nh;    // HBM
+  uint32_t* mark;  // LDS
+  D* oD;
+  size_t Sn;
 
-  for (uint32_t v = tid; v < N; v += kGBlock) {
-    dist[v] = (v == s) ? D(0) : kInf;
-#pragma unroll
-    for (int w = 0; w < W; ++w) nh[w * Sn + v] = 0u;
+  __device__ __forceinline__ LdsDistState(const GUnit<D>& u, int, D* oDist, uint32_t* oNh,
+                                          char* smem)
+      : dist(reinterpret_cast<D*>(smem)), nh(oNh + size_t(u.u0) * W * u.Sn),
+        mark(reinterpret_cast<uint32_t*>(smem + ((u.Sn * sizeof(D) + 15u) & ~size_t(15)))),
+        oD(oDist + u.u0 * u.Sn), Sn(u.Sn) {}
+  __device__ __forceinline__ Member member(uint32_t*) const {
+    return Member{mark, (uint32_t(Sn) + 31u) / 32u};
   }
-  for (uint32_t i = tid; i < 2 * mw; i += kGBlock) mark[i] = 0u;
-  if (tid == 0) {
-    q1[0] = s;
-    qcnt[0] = 0u;
-    qcnt[1] = 1u;
-    qcnt[2] = 0u;
+  __device__ __forceinline__ int words() const { return W; }
+  __device__ __forceinline__ D ld_dist(uint32_t v) const { return dist[v]; }
+  __device__ __forceinline__ D min_dist(uint32_t t, D c) { return atomicMin(&dist[t], c); }
+  __device__ __forceinline__ uint32_t ld_nh(int w, uint32_t v) const {
+    return ld_state<true>(nh + w * Sn + v);
   }
-  round_sync<true>();
-  auto weight = [&](uint64_t x) -> D {
-    return hop ? D(1) : D(static_cast<uint32_t>(x >> 32));
-  };
-  // first push of t into round r + 1's list
-  auto append = [&](uint32_t t, uint32_t r) {
-    const uint32_t bit = 1u << (t & 31u);
-    if (!(atomicOr(&mark[((r + 1) & 1) * mw + (t >> 5)], bit) & bit)) {
-      const uint32_t at = atomicAdd(&qcnt[(r + 1) % 3], 1u);
-      ((r + 1) & 1 ? q1 : q0)[at] = t;
-    }
-  };
-  auto consume = [&](uint32_t v, uint32_t r) {  // v leaves round r's list
-    atomicAnd(&mark[(r & 1) * mw + (v >> 5)], ~(1u << (v & 31u)));
-  };
+  __device__ __forceinline__ uint32_t* nh_word(int w, uint32_t v) { return nh + w * Sn + v; }
+  __device__ __forceinline__ void after_dist(const GUnit<D>& u) {
+    for (uint32_t v = threadIdx.x; v < u.N; v += kGBlock) oD[v] = dist[v];
+  }
+  __device__ __forceinline__ void after_nh(const GUnit<D>&) {}
+};
 
-  // ---- dist phase ----------------------------------------------------------
-  uint32_t r = 1, n = 1;
-  for (; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<true>(cur + i);
-      if (r > 1) consume(v, r);
-      if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
-      const D dv = dist[v];
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
-        uint64_t x[kGRow];
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          x[k] = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
-        }
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          const uint32_t lo = static_cast<uint32_t>(x[k]);
-          if (lo & OGS_EDGE_DOWN) continue;
-          const uint32_t t = edge_dst(lo);
-          const D c = dv + weight(x[k]);
-          if (c < dist[t] && c < atomicMin(&dist[t], c)) append(t, r);
-        }
-      }
-    }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
-  // the last round consumed nothing: clear both parities for the next phase
-  for (uint32_t i = tid; i < 2 * mw; i += kGBlock) mark[i] = 0u;
-  D* oD = oDist + u0 * Sn;
-  for (uint32_t v = tid; v < N; v += kGBlock) oD[v] = dist[v];
-
-  // ---- next-hop phase (words in HBM, L2 atomics) ---------------------------
-  const uint32_t r0 = r;
-  if (tid == 0) qcnt[0] = qcnt[1] = qcnt[2] = 0u;
-  round_sync<true>();
-  {
-    const uint32_t b = gRow[s] - e0, m = gRow[s + 1] - e0 - b;
-    for (uint32_t j = tid; j < m && j < 32u * W; j += kGBlock) {
-      const uint64_t x = edges[b + j];
-      const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      const uint32_t t = edge_dst(lo);
-      if (weight(x) == dist[t]) {
-        atomicOr(&nh[(j >> 5) * Sn + t], 1u << (j & 31u));
-        append(t, r0);
-      }
-    }
-  }
-  round_sync<true>();
-  n = qcnt[(r0 + 1) % 3];
-  __syncthreads();
-  for (r = r0 + 1; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = ld_state<true>(cur + i);
-      consume(v, r);
-      if (v == s || (nflags[v] & OGS_NODE_OVERLOADED)) continue;
-      const D dv = dist[v];
-      uint32_t nv[W];
-#pragma unroll
-      for (int w = 0; w < W; ++w) nv[w] = ld_state<true>(nh + w * Sn + v);
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      constexpr int kB = W <= 4 ? kGRow : 2;
-      for (uint32_t j0 = 0; j0 < m; j0 += kB) {
-        uint32_t t[kB];
-        bool ok[kB];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          const uint64_t x = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
-          const uint32_t lo = static_cast<uint32_t>(x);
-          t[k] = edge_dst(lo);
-          ok[k] = !(lo & OGS_EDGE_DOWN) && dv + weight(x) == dist[t[k]];  // tight
-        }
-        uint32_t a[kB][W];
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-#pragma unroll
-          for (int w = 0; w < W; ++w) {
-            a[k][w] = ok[k] ? nv[w] & ~ld_state<true>(nh + w * Sn + t[k]) : 0u;
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < kB; ++k) {
-          bool add = false;
-#pragma unroll
-          for (int w = 0; w < W; ++w) {
-            if (a[k][w] && (a[k][w] & ~atomicOr(&nh[w * Sn + t[k]], a[k][w]))) add = true;
-          }
-          if (add) append(t[k], r);
-        }
-      }
-    }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
-}
-
-// ---- dist AND next-hop words in LDS (N * (sizeof(D) + 4W) + one list bitset
-// <= 160 kB, e.g. 20k nodes at u32, W = 1) ----------------------------------
-// Both phases relax with LDS atomics; only the frontier lists (HBM rows) and
-// the CSR are read from L2. List membership is ONE bitset ("already in the
-// next list"), cleared in bulk at the start of every round -- behind the
-// same barrier that the round's first frontier loads are already in flight
-// across. The final distances and next-hop words are copied to the caller's
-// rows for the route kernel.
+// Distances AND next-hop words in LDS (N * (sizeof(D) + 4W) + one list bitset
+// <= 160 kB, e.g. 20k nodes at u32, W = 1): both phases relax with LDS
+// atomics; only the frontier lists (HBM rows) and the CSR are read from L2.
+// The final distances and next-hop words are copied to the caller's rows for
+// the route kernel.
 uint32_t global_lds2_bytes(uint32_t Sn, uint32_t dsize, int W) {
   return ((Sn * dsize + 15u) & ~15u) + ((Sn * 4u * uint32_t(W) + 15u) & ~15u) +
       4u * ((Sn + 31u) / 32u);
 }
 
 template <typename D, int W>
-__global__ __launch_bounds__(kGBlock) void spf_global_lds2_kernel(
-    ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags,
-    D* __restrict__ oDist, uint32_t* __restrict__ oNh, uint32_t* __restrict__ scratch) {
-  constexpr D kInf = DistInf<D>::value;
-  const int tid = threadIdx.x;
-  const uint32_t u0 = blockIdx.x;
-  const ogs_unit unit = units[u0];
-  const uint32_t s = unit.src;
-  const uint32_t nb = g.node_base[unit.topo];
-  const uint32_t N = g.node_base[unit.topo + 1] - nb;
-  const size_t Sn = size_t(g.max_nodes);
-  const uint32_t* __restrict__ gRow = g.row_ptr + nb;
-  const uint32_t e0 = gRow[0];
-  const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* __restrict__ nflags = g.node_flags + nb;
-  const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
-  uint32_t* q0 = scratch + u0 * 3 * Sn + Sn;
-  uint32_t* q1 = q0 + Sn;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  D* dist = reinterpret_cast<D*>(smem);
-  uint32_t* nh = reinterpret_cast<uint32_t*>(smem + ((Sn * sizeof(D) + 15u) & ~size_t(15)));
-  uint32_t* mark = nh + ((Sn * W + 3u) & ~size_t(3));
-  const uint32_t mw = (uint32_t(Sn) + 31u) / 32u;
-  __shared__ uint32_t qcnt[3];
+struct LdsBothState {
+  using Dist = D;
+  using Member = RoundMember;
+  static constexpr int kW = W;
+  static constexpr bool kL2Sync = true, kDistStaged = false, kNhStaged = false;
+  static constexpr int kNhStep = kGRow;
+  D* dist;         // LDS, all three
+  uint32_t* nh;
+  uint32_t* mark;
+  D* oD;
+  uint32_t* oN;
+  size_t Sn;
 
-  for (uint32_t v = tid; v < N; v += kGBlock) {
-    dist[v] = (v == s) ? D(0) : kInf;
+  __device__ __forceinline__ LdsBothState(const GUnit<D>& u, int, D* oDist, uint32_t* oNh,
+                                          char* smem)
+      : dist(reinterpret_cast<D*>(smem)),
+        nh(reinterpret_cast<uint32_t*>(smem + ((u.Sn * sizeof(D) + 15u) & ~size_t(15)))),
+        oD(oDist + u.u0 * u.Sn), oN(oNh + size_t(u.u0) * W * u.Sn), Sn(u.Sn) {
+    mark = nh + ((Sn * W + 3u) & ~size_t(3));
+  }
+  __device__ __forceinline__ Member member(uint32_t*) const {
+    return Member{mark, (uint32_t(Sn) + 31u) / 32u};
+  }
+  __device__ __forceinline__ int words() const { return W; }
+  __device__ __forceinline__ D ld_dist(uint32_t v) const { return dist[v]; }
+  __device__ __forceinline__ D min_dist(uint32_t t, D c) { return atomicMin(&dist[t], c); }
+  __device__ __forceinline__ uint32_t ld_nh(int w, uint32_t v) const { return nh[w * Sn + v]; }
+  __device__ __forceinline__ uint32_t* nh_word(int w, uint32_t v) { return nh + w * Sn + v; }
+  __device__ __forceinline__ void after_dist(const GUnit<D>&) {}
+  __device__ __forceinline__ void after_nh(const GUnit<D>& u) {
+    for (uint32_t v = threadIdx.x; v < u.N; v += kGBlock) {
+      oD[v] = dist[v];
 #pragma unroll
-    for (int w = 0; w < W; ++w) nh[w * Sn + v] = 0u;
-  }
-  if (tid == 0) {
-    q1[0] = s;
-    qcnt[0] = 0u;
-    qcnt[1] = 1u;
-    qcnt[2] = 0u;
-  }
-  round_sync<true>();
-  auto weight = [&](uint64_t x) -> D {
-    return hop ? D(1) : D(static_cast<uint32_t>(x >> 32));
-  };
-  auto append = [&](uint32_t t, uint32_t r) {  // first push of t this round
-    const uint32_t bit = 1u << (t & 31u);
-    if (!(atomicOr(&mark[t >> 5], bit) & bit)) {
-      const uint32_t at = atomicAdd(&qcnt[(r + 1) % 3], 1u);
-      ((r + 1) & 1 ? q1 : q0)[at] = t;
+      for (int w = 0; w < W; ++w) oN[w * Sn + v] = nh[w * Sn + v];
     }
-  };
-  // round r's first frontier entry per thread is loaded, then the bitset is
-  // cleared behind one barrier (the load's latency overlaps it)
-  auto begin_round = [&](const uint32_t* cur, uint32_t n) {
-    const uint32_t v0 = uint32_t(tid) < n ? ld_state<true>(cur + tid) : 0u;
-    for (uint32_t i = tid; i < mw; i += kGBlock) mark[i] = 0u;
-    __syncthreads();
-    return v0;
+  }
+};
+
+// One unit's two-phase SPF. oDist / oNh: the units' dist [Sn] and nh
+// [W * Sn] rows; scratch: stamp / q0 / q1 rows per unit (>= N entries each).
+// Wn: the next-hop word count where F::kW == kWRuntime (sources of more than
+// 512 links; rslot is never read: push-style relaxation, link slots from the
+// source's own row).
+template <class F>
+__global__ __launch_bounds__(kGBlock) void spf_global_kernel(
+    ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags, int Wn,
+    typename F::Dist* __restrict__ oDist, uint32_t* __restrict__ oNh,
+    uint32_t* __restrict__ scratch) {
+  using D = typename F::Dist;
+  constexpr int W = F::kW;
+  constexpr int kUnrollW = W == kWRuntime ? 1 : W;  // a runtime count: no unrolling
+  constexpr bool L2 = F::kL2Sync;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ uint32_t qcnt[3];
+  const uint32_t tid = threadIdx.x;
+  const GUnit<D> u(g, units[blockIdx.x], flags);
+  uint32_t* rows = scratch + u.u0 * 3 * u.Sn;
+  F st(u, Wn, oDist, oNh, smem);
+  auto mem = st.member(rows);
+  GLists fr{rows + u.Sn, u.Sn, qcnt};
+
+  for (uint32_t v = tid; v < u.N; v += kGBlock) {
+    st.dist[v] = (v == u.s) ? D(0) : DistInf<D>::value;
+#pragma unroll kUnrollW
+    for (int w = 0; w < st.words(); ++w) *st.nh_word(w, v) = 0u;
+  }
+  mem.init(u.N);
+  fr.init(u.s);
+  round_sync<L2>();
+
+  // One phase's rounds, from round r with n entries in its list: visit(v, r)
+  // for every entry. Returns the first round that was not run.
+  auto rounds = [&](uint32_t r, uint32_t n, auto&& visit) {
+    for (; n; ++r) {
+      fr.begin_round(r);
+      const uint32_t* cur = fr.list(r);
+      uint32_t v0 = 0u;
+      if constexpr (F::Member::kPerRound) {
+        // each thread's first entry is loaded, then the bitset is cleared
+        // behind one barrier (the load's latency overlaps it)
+        if (tid < n) v0 = ld_state<L2>(cur + tid);
+        mem.begin_round();
+      }
+      for (uint32_t i = tid; i < n; i += kGBlock) {
+        const uint32_t v = (F::Member::kPerRound && i == tid) ? v0 : ld_state<L2>(cur + i);
+        mem.consume(v, r);
+        visit(v, r);
+      }
+      n = fr.end_round<L2>(r);
+    }
+    return r;
   };
 
-  // ---- dist phase ----------------------------------------------------------
-  uint32_t r = 1, n = 1;
-  for (; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    const uint32_t v0 = begin_round(cur, n);
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = i == uint32_t(tid) ? v0 : ld_state<true>(cur + i);
-      if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
-      const D dv = dist[v];
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
-        uint64_t x[kGRow];
+  // ---- dist phase: rows of the nodes whose distance dropped last round ----
+  const uint32_t r0 = rounds(1u, 1u, [&](uint32_t v, uint32_t r) {
+    if (v != u.s && u.drained(v)) return;  // 741-752
+    const D dv = st.ld_dist(v);
+    const uint32_t b = u.gRow[v] - u.e0, m = u.gRow[v + 1] - u.e0 - b;
+    for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
+      const GEdges<D, kGRow> e(u, dv, b + j0, m - j0);
+      if constexpr (F::kDistStaged) {
+        // the targets' dist, then the atomicMins, then the membership
+        // atomics: one L2 round trip per step instead of one per edge and
+        // step (6.13 -> 5.65 ms on G1)
+        D seen[kGRow];
+        bool ok[kGRow];
+#pragma unroll
+        for (int k = 0; k < kGRow; ++k) seen[k] = e.up[k] ? st.ld_dist(e.t[k]) : D(0);
 #pragma unroll
         for (int k = 0; k < kGRow; ++k) {
-          x[k] = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
+          ok[k] = e.up[k] && e.c[k] < seen[k];
+          seen[k] = ok[k] ? st.min_dist(e.t[k], e.c[k]) : D(0);
         }
 #pragma unroll
         for (int k = 0; k < kGRow; ++k) {
-          const uint32_t lo = static_cast<uint32_t>(x[k]);
-          if (lo & OGS_EDGE_DOWN) continue;
-          const uint32_t t = edge_dst(lo);
-          const D c = dv + weight(x[k]);
-          if (c < dist[t] && c < atomicMin(&dist[t], c)) append(t, r);
+          ok[k] = ok[k] && e.c[k] < seen[k] && mem.first_push(e.t[k], r);
+        }
+#pragma unroll
+        for (int k = 0; k < kGRow; ++k) {
+          if (ok[k]) fr.push(e.t[k], r);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < kGRow; ++k) {
+          if (e.up[k] && e.c[k] < st.ld_dist(e.t[k]) && e.c[k] < st.min_dist(e.t[k], e.c[k]) &&
+              mem.first_push(e.t[k], r)) {
+            fr.push(e.t[k], r);
+          }
         }
       }
     }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
+  });
+  st.after_dist(u);
 
-  // ---- next-hop phase ------------------------------------------------------
-  const uint32_t r0 = r;
-  if (tid == 0) qcnt[0] = qcnt[1] = qcnt[2] = 0u;
-  for (uint32_t i = tid; i < mw; i += kGBlock) mark[i] = 0u;
-  __syncthreads();
+  // ---- next-hop phase: the source's row seeds link slots, tight pushes ----
+  fr.reset();
+  mem.reset();
+  round_sync<L2>();
   {
-    const uint32_t b = gRow[s] - e0, m = gRow[s + 1] - e0 - b;
-    for (uint32_t j = tid; j < m && j < 32u * W; j += kGBlock) {
-      const uint64_t x = edges[b + j];
+    const uint32_t b = u.gRow[u.s] - u.e0, m = u.gRow[u.s + 1] - u.e0 - b;
+    for (uint32_t j = tid; j < m && j < 32u * uint32_t(st.words()); j += kGBlock) {
+      const uint64_t x = u.edges[b + j];
       const uint32_t lo = static_cast<uint32_t>(x);
       if (lo & OGS_EDGE_DOWN) continue;
       const uint32_t t = edge_dst(lo);
-      if (weight(x) == dist[t]) {
-        atomicOr(&nh[(j >> 5) * Sn + t], 1u << (j & 31u));
-        append(t, r0);
+      if (u.weight(x) == st.ld_dist(t)) {
+        atomicOr(st.nh_word(j >> 5, t), 1u << (j & 31u));
+        if (mem.first_push(t, r0)) fr.push(t, r0);
       }
     }
   }
-  round_sync<true>();
-  n = qcnt[(r0 + 1) % 3];
-  __syncthreads();
-  for (r = r0 + 1; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint32_t* cur = (r & 1) ? q1 : q0;
-    const uint32_t v0 = begin_round(cur, n);
-    for (uint32_t i = tid; i < n; i += kGBlock) {
-      const uint32_t v = i == uint32_t(tid) ? v0 : ld_state<true>(cur + i);
-      if (v == s || (nflags[v] & OGS_NODE_OVERLOADED)) continue;
-      const D dv = dist[v];
-      uint32_t nv[W];
+  rounds(r0 + 1, fr.end_round<L2>(r0), [&](uint32_t v, uint32_t r) {
+    if (v == u.s || u.drained(v)) return;
+    const D dv = st.ld_dist(v);
+    uint32_t nv[kUnrollW];  // NH(v); with a runtime word count re-read per edge
+    if constexpr (W != kWRuntime) {
 #pragma unroll
-      for (int w = 0; w < W; ++w) nv[w] = nh[w * Sn + v];
-      const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
-      for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
-        uint64_t x[kGRow];
+      for (int w = 0; w < W; ++w) nv[w] = st.ld_nh(w, v);
+    }
+    const uint32_t b = u.gRow[v] - u.e0, m = u.gRow[v + 1] - u.e0 - b;
+    constexpr int kB = F::kNhStep;
+    for (uint32_t j0 = 0; j0 < m; j0 += kB) {
+      const GEdges<D, kB> e(u, dv, b + j0, m - j0);
+      if constexpr (F::kNhStaged) {
+        bool ok[kB], add[kB];
 #pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          x[k] = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
+        for (int k = 0; k < kB; ++k) ok[k] = e.up[k] && e.c[k] == st.ld_dist(e.t[k]);  // tight
+        uint32_t a[kB][kUnrollW];
+#pragma unroll
+        for (int k = 0; k < kB; ++k) {
+#pragma unroll
+          for (int w = 0; w < W; ++w) a[k][w] = ok[k] ? nv[w] & ~st.ld_nh(w, e.t[k]) : 0u;
         }
 #pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-          const uint32_t lo = static_cast<uint32_t>(x[k]);
-          if (lo & OGS_EDGE_DOWN) continue;
-          const uint32_t t = edge_dst(lo);
-          if (dv + weight(x[k]) != dist[t]) continue;  // not tight
-          bool add = false;
+        for (int k = 0; k < kB; ++k) {
+          add[k] = false;
 #pragma unroll
           for (int w = 0; w < W; ++w) {
-            const uint32_t a = nv[w] & ~nh[w * Sn + t];
-            if (a && (a & ~atomicOr(&nh[w * Sn + t], a))) add = true;
+            if (a[k][w] && (a[k][w] & ~atomicOr(st.nh_word(w, e.t[k]), a[k][w]))) add[k] = true;
           }
-          if (add) append(t, r);
+        }
+#pragma unroll
+        for (int k = 0; k < kB; ++k) add[k] = add[k] && mem.first_push(e.t[k], r);
+#pragma unroll
+        for (int k = 0; k < kB; ++k) {
+          if (add[k]) fr.push(e.t[k], r);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < kB; ++k) {
+          if (!e.up[k] || e.c[k] != st.ld_dist(e.t[k])) continue;  // not tight
+          bool add = false;
+#pragma unroll kUnrollW
+          for (int w = 0; w < st.words(); ++w) {
+            uint32_t a;
+            if constexpr (W == kWRuntime) a = st.ld_nh(w, v); else a = nv[w];
+            a &= ~st.ld_nh(w, e.t[k]);
+            if (a && (a & ~atomicOr(st.nh_word(w, e.t[k]), a))) add = true;
+          }
+          if (add && mem.first_push(e.t[k], r)) fr.push(e.t[k], r);
         }
       }
     }
-    round_sync<true>();
-    n = qcnt[(r + 1) % 3];
-    __syncthreads();
-  }
-  D* oD = oDist + u0 * Sn;
-  uint32_t* oN = oNh + u0 * W * Sn;
-  for (uint32_t v = tid; v < N; v += kGBlock) {
-    oD[v] = dist[v];
-#pragma unroll
-    for (int w = 0; w < W; ++w) oN[w * Sn + v] = nh[w * Sn + v];
-  }
+  });
+  st.after_nh(u);
 }
 
 // ---- one phase, packed {dist, next-hop word} in LDS (W = 1, u32 distances;
@@ -881,8 +626,6 @@ __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
   }
 }
 
-hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
-
 // "spf_global" option: 0 (default) the global path only where the LDS paths
 // cannot hold a unit, 1 every ogs_spf_routes call (A/B, parity tests).
 // EngineOptions::spfGlobal (engine.h), default 0
@@ -891,9 +634,9 @@ hipError_t workspace(size_t bytes, hipStream_t stream, void** out);
 // EngineOptions::spfGlobalSync (engine.h), default 1
 // "spf_global_lds": 1 (default) the best LDS form that fits -- one-phase
 // packed {dist, nh} words (spf_global_lds3_kernel, W = 1, u32), else
-// distances and next-hop words in two phases (spf_global_lds2_kernel), else
-// distances only (spf_global_lds_kernel); 3 the two-phase form, 2 distances
-// only, 0 always the all-HBM form (A/B)
+// distances and next-hop words in two phases (LdsBothState), else distances
+// only (LdsDistState); 3 the two-phase form, 2 distances only, 0 always the
+// all-HBM form (A/B)
 // EngineOptions::spfGlobalLds (engine.h), default 1
 
 // Does the LDS-resident workgroup path fit a unit of this graph? (the last
@@ -905,8 +648,6 @@ bool lds_unit_fits(const ogs_graph& g, int W, uint32_t flags) {
   return b <= 160u * 1024u;
 }
 
-uint32_t frontier_lds_bytes(uint32_t Sn, int W, bool queue, bool ninfo, bool stamp8);
-
 bool use_global(const ogs_graph& g, int W, uint32_t flags) {
   if (opts().spfGlobal == 1 || !lds_unit_fits(g, W, flags)) return true;
   // past the frontier kernel's LDS budget the remaining LDS paths sweep
@@ -917,70 +658,70 @@ bool use_global(const ogs_graph& g, int W, uint32_t flags) {
       frontier_lds_bytes(uint32_t(g.max_nodes), W, false, true, false) > 160u * 1024u;
 }
 
+// SPF (+ RouteDb when pt has prefixes) of every unit with W-word next-hop
+// sets (W == kWRuntime: Wn words, all state in HBM). dist / nh are the
+// caller's rows where given, else workspace, followed by the units' scratch.
 template <typename D, int W>
 hipError_t launch_global_w(const ogs_graph& g, const ogs_prefix_table* pt,
-                           const ogs_unit* units, int nUnits, uint32_t flags,
+                           const ogs_unit* units, int nUnits, uint32_t flags, int Wn,
                            const ogs_spf_out& out, hipStream_t stream) {
-  const size_t Sn = size_t(g.max_nodes);
-  const size_t U = size_t(nUnits);
-  auto r256 = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t distBytes = out.dist ? 0 : r256(U * Sn * sizeof(D));
-  const size_t nhBytes = out.nh ? 0 : r256(U * W * Sn * 4);
-  const size_t scratchBytes = r256(U * 3 * Sn * 4);
+  const size_t Sn = size_t(g.max_nodes), U = size_t(nUnits);
+  const size_t distBytes = out.dist ? 0 : round256(U * Sn * sizeof(D));
+  const size_t nhBytes = out.nh ? 0 : round256(U * Wn * Sn * 4);
   void* ws = nullptr;
-  hipError_t e = workspace(distBytes + nhBytes + scratchBytes, stream, &ws);
+  hipError_t e = workspace(distBytes + nhBytes + round256(U * 3 * Sn * 4), stream, &ws);
   if (e != hipSuccess) return e;
   char* base = static_cast<char*>(ws);
   D* dist = out.dist ? static_cast<D*>(out.dist) : reinterpret_cast<D*>(base);
   uint32_t* nh = out.nh ? out.nh : reinterpret_cast<uint32_t*>(base + distBytes);
   uint32_t* scratch = reinterpret_cast<uint32_t*>(base + distBytes + nhBytes);
-  const uint32_t lds = global_lds_bytes(uint32_t(Sn), sizeof(D));
-  const uint32_t lds2 = global_lds2_bytes(uint32_t(Sn), sizeof(D), W);
-  const uint32_t lds3 = global_lds3_bytes(uint32_t(Sn));
-  if constexpr (W == 1 && sizeof(D) == 4) {
-    if (opts().spfGlobalLds == 1 && opts().spfGlobalSync && lds3 <= 160u * 1024u) {
-      auto k = spf_global_lds3_kernel;
-      if (lds3 > 64u * 1024u) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds3));
-        if (e != hipSuccess) return e;
-      }
-      // the route pass runs inside the launch (no separate route kernel)
-      const ogs_prefix_table ptv = pt ? *pt : ogs_prefix_table{};
-      hipLaunchKernelGGL(k, dim3(nUnits), dim3(kGBlock), lds3, stream, g, units, flags,
-                         reinterpret_cast<uint32_t*>(dist), nh, scratch, ptv, out);
-      return hipGetLastError();
-    }
-  }
-  if ((opts().spfGlobalLds == 1 || opts().spfGlobalLds == 3) && opts().spfGlobalSync && lds2 <= 160u * 1024u) {
-    auto k = spf_global_lds2_kernel<D, W>;
-    if (lds2 > 64u * 1024u) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, int(lds2));
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(nUnits), dim3(kGBlock), lds2, stream, g, units, flags, dist, nh,
-                       scratch);
-  } else if ((opts().spfGlobalLds == 1 || opts().spfGlobalLds == 2) && opts().spfGlobalSync &&
-             lds <= 160u * 1024u) {
-    auto k = spf_global_lds_kernel<D, W>;
-    if (lds > 64u * 1024u) {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(nUnits), dim3(kGBlock), lds, stream, g, units, flags, dist, nh,
-                       scratch);
-  } else if (opts().spfGlobalSync) {
-    hipLaunchKernelGGL((spf_global_kernel<D, W, true>), dim3(nUnits), dim3(kGBlock), 0, stream,
-                       g, units, flags, dist, nh, scratch);
+  auto run = [&](auto k, uint32_t ldsBytes) {
+    return launch_dyn_lds(k, dim3(nUnits), dim3(kGBlock), ldsBytes, stream, g, units, flags, Wn,
+                          dist, nh, scratch);
+  };
+  if constexpr (W == kWRuntime) {
+    e = run(spf_global_kernel<HbmState<D, W, true>>, 0);
+    if (e != hipSuccess || !pt || pt->max_prefixes == 0) return e;
+    return launch_route_global_wide<D>(g, *pt, units, nUnits, flags, Wn, dist, nh, out, stream);
   } else {
-    hipLaunchKernelGGL((spf_global_kernel<D, W, false>), dim3(nUnits), dim3(kGBlock), 0, stream,
-                       g, units, flags, dist, nh, scratch);
+    constexpr uint32_t kLds = 160u * 1024u;
+    const int form = opts().spfGlobalLds;
+    const bool sync = opts().spfGlobalSync;
+    const uint32_t lds = global_lds_bytes(uint32_t(Sn), sizeof(D));
+    const uint32_t lds2 = global_lds2_bytes(uint32_t(Sn), sizeof(D), W);
+    const uint32_t lds3 = global_lds3_bytes(uint32_t(Sn));
+    if constexpr (W == 1 && sizeof(D) == 4) {
+      if (form == 1 && sync && lds3 <= kLds) {
+        // the route pass runs inside the launch (no separate route kernel)
+        const ogs_prefix_table ptv = pt ? *pt : ogs_prefix_table{};
+        return launch_dyn_lds(spf_global_lds3_kernel, dim3(nUnits), dim3(kGBlock), lds3, stream,
+                              g, units, flags, reinterpret_cast<uint32_t*>(dist), nh, scratch,
+                              ptv, out);
+      }
+    }
+    if ((form == 1 || form == 3) && sync && lds2 <= kLds) {
+      e = run(spf_global_kernel<LdsBothState<D, W>>, lds2);
+    } else if ((form == 1 || form == 2) && sync && lds <= kLds) {
+      e = run(spf_global_kernel<LdsDistState<D, W>>, lds);
+    } else if (sync) {
+      e = run(spf_global_kernel<HbmState<D, W, true>>, 0);
+    } else {
+      e = run(spf_global_kernel<HbmState<D, W, false>>, 0);
+    }
+    if (e != hipSuccess || !pt || pt->max_prefixes == 0) return e;
+    return launch_route_global<D, W>(g, *pt, units, nUnits, flags, dist, nh, out, stream);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess || !pt || pt->max_prefixes == 0) return e;
-  return launch_route_global<D, W>(g, *pt, units, nUnits, flags, dist, nh, out, stream);
+}
+
+// SPF (+ RouteDb) with next-hop sets of any width (past 16 words, or a width
+// that is no power of two).
+hipError_t launch_spf_routes_global_wide(const ogs_graph& g, const ogs_prefix_table* pt,
+                                         const ogs_unit* units, int nUnits, uint32_t flags,
+                                         int W, const ogs_spf_out& out, hipStream_t stream) {
+  if (flags & OGS_F_WIDE_METRIC) {
+    return launch_global_w<uint64_t, kWRuntime>(g, pt, units, nUnits, flags, W, out, stream);
+  }
+  return launch_global_w<uint32_t, kWRuntime>(g, pt, units, nUnits, flags, W, out, stream);
 }
 
 template <typename D>
@@ -988,12 +729,12 @@ hipError_t launch_global_d(const ogs_graph& g, const ogs_prefix_table* pt,
                            const ogs_unit* units, int nUnits, uint32_t flags, int W,
                            const ogs_spf_out& out, hipStream_t stream) {
   switch (W) {
-    case 1: return launch_global_w<D, 1>(g, pt, units, nUnits, flags, out, stream);
-    case 2: return launch_global_w<D, 2>(g, pt, units, nUnits, flags, out, stream);
-    case 4: return launch_global_w<D, 4>(g, pt, units, nUnits, flags, out, stream);
-    case 8: return launch_global_w<D, 8>(g, pt, units, nUnits, flags, out, stream);
-    case 16: return launch_global_w<D, 16>(g, pt, units, nUnits, flags, out, stream);
-    default: return launch_global_wide<D>(g, pt, units, nUnits, flags, W, out, stream);
+    case 1: return launch_global_w<D, 1>(g, pt, units, nUnits, flags, W, out, stream);
+    case 2: return launch_global_w<D, 2>(g, pt, units, nUnits, flags, W, out, stream);
+    case 4: return launch_global_w<D, 4>(g, pt, units, nUnits, flags, W, out, stream);
+    case 8: return launch_global_w<D, 8>(g, pt, units, nUnits, flags, W, out, stream);
+    case 16: return launch_global_w<D, 16>(g, pt, units, nUnits, flags, W, out, stream);
+    default: return launch_global_w<D, kWRuntime>(g, pt, units, nUnits, flags, W, out, stream);
   }
 }
 

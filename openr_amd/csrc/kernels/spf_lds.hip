@@ -37,6 +37,7 @@
 #include "spf_lds.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -106,13 +107,12 @@ struct LdsScratch {
 };
 
 __host__ LdsScratch lds_scratch(const ogs_graph& g, const LdsImage& L, int nUnits) {
-  auto r256 = [](size_t x) { return (x + 255u) & ~size_t(255); };
   LdsScratch S{};
   S.nEB = (uint32_t(std::max(g.max_edges, 1)) + kPrepEdges - 1u) / kPrepEdges;
-  S.mm = r256(size_t(g.num_topos) * L.stride);
-  S.ctr = S.mm + r256(size_t(g.num_topos) * S.nEB * 16u);
+  S.mm = round256(size_t(g.num_topos) * L.stride);
+  S.ctr = S.mm + round256(size_t(g.num_topos) * S.nEB * 16u);
   S.ready = S.ctr + 256u;
-  S.bytes = S.ready + r256(size_t(std::max(nUnits, 1)) * 4u);
+  S.bytes = S.ready + round256(size_t(std::max(nUnits, 1)) * 4u);
   return S;
 }
 

@@ -37,6 +37,7 @@
 #include "route_core.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -134,16 +135,8 @@ hipError_t launch_one(const ogs_graph& g, const ogs_prefix_table& pt,
   constexpr int upb = kBlock / UT;
   const int grid = (nUnits + upb - 1) / upb;
   const size_t lds = size_t(ldsPerUnit) * upb;
-  auto k = spf_route_kernel<D, W, UT, STAGE>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k),
-        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, g, pt,
-                     hasPrefixes, units, nUnits, flags, out, ldsPerUnit);
-  return hipGetLastError();
+  return launch_dyn_lds(spf_route_kernel<D, W, UT, STAGE>, dim3(grid), dim3(kBlock), lds,
+                        stream, g, pt, hasPrefixes, units, nUnits, flags, out, ldsPerUnit);
 }
 
 uint32_t lds_per_unit(int maxNodes, int maxEdges, int W, int distBytes,
@@ -194,43 +187,11 @@ hipError_t dispatch_d(int W, const ogs_graph& g, const ogs_prefix_table& pt,
   }
 }
 
-template <typename D, int W>
-bool try_small(const ogs_graph& g, const ogs_prefix_table& pt, int hasPrefixes,
-               const ogs_unit* units, int nUnits, uint32_t flags,
-               const ogs_spf_out& out, int maxDegree, uint32_t maxA,
-               int unitWidth, hipStream_t stream, hipError_t* err);
-
-bool try_wave(const ogs_graph& g, const ogs_prefix_table& pt, int hasPrefixes,
-              const ogs_unit* units, int nUnits, uint32_t flags,
-              const ogs_spf_out& out, uint32_t maxA, hipStream_t stream,
-              hipError_t* err);
-
-bool try_frontier(const ogs_graph& g, const ogs_unit* units, int nUnits,
-                  uint32_t flags, int W, uint32_t* dist, uint32_t* nh,
-                  hipStream_t stream, hipError_t* err);
-bool try_ms_stream(const ogs_graph& g, const ogs_prefix_table& pt,
-                   const ogs_unit* units, int nUnits, uint32_t flags, int W,
-                   const ogs_spf_out& out, hipStream_t stream, hipError_t* err);
-bool try_ms(const ogs_graph& g, const ogs_prefix_table& pt, int hasPrefixes,
-            const ogs_unit* units, int nUnits, uint32_t flags, int W,
-            const ogs_spf_out& out, hipStream_t stream, hipError_t* err);
-
 // unit_width option / OGS_UNIT_WIDTH env: -1 automatic, 0 generic kernel
 // only, 1 wave kernel, 2 small kernel (automatic width), 3 multi-source
 // edge-parallel kernel, 64/128/256 small kernel at that unit width.
 // EngineOptions::unitWidth (engine.h), default $OGS_UNIT_WIDTH or -1
 int small_unit_width() { return opts().unitWidth; }
-
-bool use_global(const ogs_graph& g, int W, uint32_t flags);
-hipError_t launch_spf_routes_exact(const ogs_graph& g, const ogs_prefix_table* pt,
-                                   const ogs_unit* units, int nUnits, uint32_t flags,
-                                   int W, const ogs_spf_out& out, hipStream_t stream);
-hipError_t launch_spf_routes_global(const ogs_graph& g, const ogs_prefix_table* pt,
-                                    const ogs_unit* units, int nUnits, uint32_t flags,
-                                    int W, const ogs_spf_out& out, hipStream_t stream);
-hipError_t launch_spf_routes_global_wide(const ogs_graph& g, const ogs_prefix_table* pt,
-                                         const ogs_unit* units, int nUnits, uint32_t flags,
-                                         int W, const ogs_spf_out& out, hipStream_t stream);
 
 hipError_t launch_spf_routes(const ogs_graph& g, const ogs_prefix_table* pt,
                              const ogs_unit* units, int nUnits,

@@ -32,6 +32,7 @@
 #include "route_core.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -280,16 +281,8 @@ hipError_t launch_ms(const ogs_graph& g, const ogs_prefix_table& pt,
                      int hasPrefixes, const ogs_unit* units, int nUnits,
                      uint32_t flags, const ogs_spf_out& out, hipStream_t stream) {
   const size_t lds = ms_lds_bytes(g.max_nodes, G, W);
-  auto k = spf_route_ms_kernel<G, W>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       int(lds));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3((nUnits + G - 1) / G), dim3(kBlock), lds, stream,
-                     g, pt, hasPrefixes, units, nUnits, flags, out);
-  return hipGetLastError();
+  return launch_dyn_lds(spf_route_ms_kernel<G, W>, dim3((nUnits + G - 1) / G), dim3(kBlock), lds,
+                        stream, g, pt, hasPrefixes, units, nUnits, flags, out);
 }
 
 // "ms_group" option: 0 automatic, else force G (1, 2 or 4) when it fits.

@@ -25,6 +25,7 @@
 #include "openr_gpu.h"
 #include "route_core.h"
 #include "spf_core.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -362,16 +363,8 @@ hipError_t launch_small(const ogs_graph& g, const ogs_prefix_table& pt,
   constexpr int upb = threads / UT;
   const int grid = (nUnits + upb - 1) / upb;
   const size_t bytes = size_t(lds) * upb;
-  auto k = spf_route_small_kernel<D, W, UT, NPL, MAXD>;
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k),
-        hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(threads), bytes, stream, g, pt,
-                     hasPrefixes, units, nUnits, flags, out, lds, maxA);
-  return hipGetLastError();
+  return launch_dyn_lds(spf_route_small_kernel<D, W, UT, NPL, MAXD>, dim3(grid), dim3(threads),
+                        bytes, stream, g, pt, hasPrefixes, units, nUnits, flags, out, lds, maxA);
 }
 
 // Returns true (and launches) when the small path applies.

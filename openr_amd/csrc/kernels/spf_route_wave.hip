@@ -34,6 +34,7 @@
 #include "route_core.h"
 #include "spf_core.h"
 #include "engine.h"
+#include "launch.h"
 
 namespace ogs {
 
@@ -859,17 +860,10 @@ hipError_t launch_wave_upb(const ogs_graph& g, const ogs_prefix_table& pt,
   const int grid = (nUnits + UPB - 1) / UPB;
   size_t bytes = size_t(lds) * UPB;
   if (bytes < size_t(opts().waveWgLds)) bytes = size_t(opts().waveWgLds);
-  auto k = spf_route_wave_kernel<NPL, MAXD, UPB>;
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k),
-        hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes));
-    if (e != hipSuccess) return e;
-  }
   if (opts().routeStoreNt & 2) flags |= kFlagNtStores;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(64 * UPB), bytes, stream, g, pt,
-                     hasPrefixes, units, nUnits, flags, out, lds, maxA, uint32_t(opts().waveOpt));
-  return hipGetLastError();
+  return launch_dyn_lds(spf_route_wave_kernel<NPL, MAXD, UPB>, dim3(grid), dim3(64 * UPB), bytes,
+                        stream, g, pt, hasPrefixes, units, nUnits, flags, out, lds, maxA,
+                        uint32_t(opts().waveOpt));
 }
 
 template <int NPL, int MAXD>

@@ -50,6 +50,50 @@ def test_forced_global_both_state_forms(product, oracle, lds):
              oracle.gen_route_dbs("fabric", fab, fsrc, True, True, False), f"fabric{lds}")
 
 
+LONG_FAB = dict(pods=32, planes=2, sswPerPlane=4, rswPerPod=48, full=True, prefixesPerNode=1,
+                nodeOverloadPermille=20)
+LONG_SRCS = ["1-0-0", "2-3-1", "3-31-47"]  # 32 links (one word), 52 (two words), 2
+
+
+@pytest.fixture(scope="module")
+def long_list_want(oracle):
+    """The oracle's RouteDbs of the long-list fabric, and -- from its SPF
+    result on the same fabric without the prefix mix (its own seed: topology
+    and overloads are the same), where each node's one prefix has one
+    advertiser and unit metrics make a route's metric the node's hop distance
+    -- the largest number of nodes at one hop distance per source."""
+    layer = []
+    for db in oracle.gen_route_dbs("fabric", LONG_FAB, LONG_SRCS, True, True, False):
+        lines = db.decode().splitlines()
+        hops = [int(lines[i + 1].split(" m=")[1].split()[0])
+                for i, l in enumerate(lines) if l.startswith("U ")]
+        layer.append(max(hops.count(h) for h in set(hops)))
+    return oracle.gen_route_dbs("fabric", dict(LONG_FAB, **MIX), LONG_SRCS, True, True, False), layer
+
+
+@pytest.mark.parametrize("opts", [dict(spf_global_lds=1), dict(spf_global_lds=3),
+                                  dict(spf_global_lds=2), dict(spf_global_lds=0),
+                                  dict(spf_global_lds=0, spf_global_sync=0)],
+                         ids=lambda o: "-".join(f"{k[11:]}{v}" for k, v in o.items()))
+def test_forced_global_long_lists(product, long_list_want, opts):
+    """Frontier lists longer than the 1,024-thread workgroup, in every state
+    form: the second pass of the list loop, and the per-round bitset's "first
+    entry prefetched, later ones loaded" branch. A 1,608-node fabric with
+    unit metrics (32 pods x 48 rack switches, 2 planes x 4 spines); the nodes
+    at hop distance d are round d + 1's list. From spine 1-0-0, 1,539 nodes
+    are at distance 2 (round 3: the 32 x 48 rack switches of the plane-0
+    fabric switches and 3 spines); from fabric switch 2-3-1, 1,396 at
+    distance 3 (31 x 48 rack switches, less the 96 behind two hard-drained
+    fabric switches, which relax nothing, plus 4 spines); from rack switch
+    3-31-47, 1,488 at distance 4 (counted from the oracle's SPF result, and
+    asserted here)."""
+    want, layer = long_list_want
+    assert layer == [1539, 1396, 1488] and min(layer) > 1024
+    with capi.scoped_options(spf_global=1, **opts):
+        got = product.gen_route_dbs("fabric", dict(LONG_FAB, **MIX), LONG_SRCS, True, True, False)
+    _cmp(got, want, f"long{opts}")
+
+
 @pytest.mark.parametrize("brs", [False, True])
 def test_forced_global_grid_all_sources(product, oracle, brs):
     opts = dict(n=7, metricSeed=0xC2000077, prefixSeed=5, adjOverloadPermille=30,

@@ -1,7 +1,9 @@
 """A/B of the global-state SPF path on the G1 workload (20,000-node WAN, 64
-sources, one launch): option OPT (default spf_global_sync) at the values in
-VALS, interleaved in one process; prints median launch time per value and
-checks every value's RouteDb digest equals the golden one."""
+sources, one launch): the variants given as arguments, each a comma-separated
+list of name=value (ogs_set_option), e.g. "spf_global_lds=0,spf_global_sync=0",
+interleaved in one process; prints median launch time per variant and checks
+every variant's RouteDb digest equals the golden one. Without arguments:
+option $OPT (default spf_global_sync) at the values in $VALS (default 0,1)."""
 import json
 import os
 import sys
@@ -20,7 +22,7 @@ def main():
     from openr_amd.workloads import G1_OPTS, G1_SOURCES
     openr_amd.require_gpu()
     opt = os.environ.get("OPT", "spf_global_sync")
-    vals = [int(x) for x in os.environ.get("VALS", "0,1").split(",")]
+    vals = sys.argv[1:] or [f"{opt}={x}" for x in os.environ.get("VALS", "0,1").split(",")]
     lib = capi.load()
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "bench_digests.json"))).get("g1")
     br = openr_amd.decision.BatchRunner(True, False, False)
@@ -29,7 +31,8 @@ def main():
     times = {v: [] for v in vals}
     for rnd in range(6):
         for v in vals:
-            with capi.scoped_options(lib, **{opt: v}):
+            with capi.scoped_options(lib, **{k: int(x) for k, x in
+                                             (kv.split("=") for kv in v.split(","))}):
                 t0 = time.perf_counter()
                 br.run()
                 dt = time.perf_counter() - t0
@@ -39,7 +42,7 @@ def main():
                 br.download()
                 d = shard.combine_digests(br.unit_digest(u, G1_SOURCES[u])
                                           for u in range(len(G1_SOURCES)))
-                print(f"{opt}={v}: median {median(times[v]) * 1e3:.3f} ms "
+                print(f"{v}: median {median(times[v]) * 1e3:.3f} ms "
                       f"min {min(times[v]) * 1e3:.3f} ms digest {d:016x} "
                       f"golden={'match' if f'{d:016x}' == golden else 'MISMATCH'}", flush=True)
 
