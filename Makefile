@@ -72,10 +72,11 @@ SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fr
 ASAN_BIN := build/asan/host_asan
 ASAN_REF := build/asan/_refcpu$(EXT)
 ASAN_LOG ?= profiles/r06_asan.log
-$(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp
+$(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
-	  $(HOST) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp -o $@ -lpthread
+	  $(HOST) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp \
+	  -o $@ -lpthread
 $(ASAN_REF): oracle/refcpu/refcpu.cpp oracle/refcpu/refcpu.h oracle/refcpu/bindings.cpp openr_amd/csrc/gen/topogen.h
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -fPIC -shared -I$(PY_INC) -I$(PYBIND_INC) \

@@ -53,8 +53,9 @@ extern "C" {
  * ogs_spf_routes_variants writes ogs_route_diff.base_desc_valid back. 5:
  * ogs_spf_routes_groups / ogs_route_group. 6: execution contexts
  * (ogs_ctx_create / ogs_ctx_set_option / ogs_ctx_* compute calls). 7: knob
- * read-back (ogs_get_option / ogs_ctx_get_option / ogs_option_name). */
-#define OGS_ABI_VERSION 7
+ * read-back (ogs_get_option / ogs_ctx_get_option / ogs_option_name).
+ * 8: ogs_route_delta. */
+#define OGS_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------ */
 #define OGS_OK 0
@@ -554,6 +555,73 @@ int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
                              int32_t max_prefixes, const ogs_spf_out* records,
                              int32_t nh_words, const ogs_route_changes* changes,
                              void* stream);
+
+/* Route delta of ONE source between two builds (ABI 8): what
+ * Decision::rebuildRoutes' full branch (Decision.cpp:912-927) gets from
+ * buildRouteDb + DecisionRouteDb::calculateUpdate (SpfSolver.cpp:21-56)
+ * against the RouteDb it holds, computed from the two builds' device records.
+ * `prev` and `next` are record sets of the SAME prefix table and source row
+ * (one unit: meta [P], metric [P], mask [W*P], sel [P], all required); the
+ * call writes the compact, prefix-ascending list of the records of `next`
+ * that differ, each with a kind word:
+ *   OGS_DELTA_ROUTE      the route differs as RibUnicastEntry::operator==
+ *                        (RibEntry.h:81-87) sees it -- ogs_route_diff's rule:
+ *                        validity, or both valid and the LOCAL bit, the best
+ *                        entry (by adv_class through adv_off when given, else
+ *                        by best index + DRAINED), the metric, a mask word
+ *                        or, with policy columns, applied / counter;
+ *   OGS_DELTA_SELECTION  the SELECTED bit, the best index, the DRAINED bit or
+ *                        the sel word differ (getBestRoutesCache()).
+ * A ROUTE record whose meta lacks OGS_ROUTE_VALID is a deletion. */
+#define OGS_DELTA_ROUTE 0x1u
+#define OGS_DELTA_SELECTION 0x2u
+/* prefixes per tile; the workspace (device, 4-byte aligned, contents
+ * undefined before and after) holds 16 B of counts and two 64-word bitmaps
+ * per tile */
+#define OGS_ROUTE_DELTA_TILE 2048
+#define OGS_ROUTE_DELTA_WORKSPACE_BYTES(num_prefixes) \
+  ((((size_t)(num_prefixes) + OGS_ROUTE_DELTA_TILE - 1) / OGS_ROUTE_DELTA_TILE) * (size_t)528)
+
+/* RibPolicy statement choices of both builds (ogs_rib_policy_apply's applied
+ * / counter columns, [P] each): all four, or no ogs_route_delta_policy. */
+typedef struct ogs_route_delta_policy {
+  const uint16_t* prev_applied;
+  const uint16_t* prev_counter;
+  const uint16_t* next_applied;
+  const uint16_t* next_counter;
+} ogs_route_delta_policy;
+
+/* Caller-owned device outputs. Records past `capacity` are not written;
+ * header[0] still carries the true count. */
+typedef struct ogs_route_delta_out {
+  uint32_t capacity; /* records the arrays below hold (mask stride)       */
+  uint32_t* prefix;  /* [capacity] prefix index, ascending                */
+  uint32_t* kind;    /* [capacity] OGS_DELTA_* bits                       */
+  uint32_t* meta;    /* [capacity] next's meta                            */
+  void* metric;      /* [capacity] uint32 (uint64 with OGS_F_WIDE_METRIC) */
+  uint32_t* mask;    /* [nh_words * capacity] word w of record i at
+                        mask[w * capacity + i]                            */
+  uint32_t* sel;     /* [capacity]                                        */
+  uint16_t* applied; /* [capacity] next's columns: required with a        */
+  uint16_t* counter; /* policy, ignored without                           */
+  uint32_t* header;  /* [4] {total records, ROUTE records to update (next
+                        valid), routes to delete (prev valid, next not),
+                        no_route: records of ALL of next whose reason is
+                        UNREACHABLE or NO_NEXTHOP
+                        (decision.no_route_to_prefix)}                    */
+} ogs_route_delta_out;
+
+/* Two launches on `stream` (mark, then an ordered gather: no workgroup waits
+ * on another), no host round trip between them. adv_off [P+1] / adv_class
+ * [2*A] as ogs_prefix_table.adv_off of the one topology and
+ * ogs_route_diff.adv_class, both or neither. flags: OGS_F_WIDE_METRIC only.
+ * nh_words 1, 2 or 4 (else OGS_E_UNSUPPORTED). num_prefixes == 0: OGS_OK,
+ * nothing read or written. No ogs_ctx_ form: the call uses no engine scratch
+ * and no knob. */
+int ogs_route_delta(const ogs_spf_out* prev, const ogs_spf_out* next, int32_t num_prefixes,
+                    const uint32_t* adv_off, const uint32_t* adv_class,
+                    const ogs_route_delta_policy* policy, uint32_t flags, int32_t nh_words,
+                    const ogs_route_delta_out* out, void* workspace, void* stream);
 
 /* Incremental CSR update: edges[idx[i]] = val[i] for
  * i < n, idx / val device arrays (encoded as ogs_graph.edges). Replaces the

@@ -7,12 +7,17 @@ import ctypes
 from . import LIB_PATH
 
 OGS_OK = 0
-OGS_ABI_VERSION = 7  # include/openr_gpu.h
+OGS_ABI_VERSION = 8  # include/openr_gpu.h
 OGS_F_ENABLE_V4 = 0x01
 OGS_F_V4_OVER_V6 = 0x02
 OGS_F_BEST_ROUTE_SELECTION = 0x04
 OGS_F_HOP_METRIC = 0x08
 OGS_F_WIDE_METRIC = 0x10
+OGS_E_INVALID = -1
+OGS_E_UNSUPPORTED = -4
+OGS_DELTA_ROUTE = 0x1
+OGS_DELTA_SELECTION = 0x2
+OGS_ROUTE_DELTA_TILE = 2048
 
 # every extern "C" entry point declared in include/openr_gpu.h
 EXPORTS = [
@@ -28,6 +33,7 @@ EXPORTS = [
     "ogs_ctx_ksp_paths", "ogs_ctx_ksp2_paths", "ogs_ctx_routes_multiarea",
     "ogs_ctx_rib_policy_apply",
     "ogs_get_option", "ogs_ctx_get_option", "ogs_option_name",
+    "ogs_route_delta",
 ]
 
 
@@ -62,6 +68,24 @@ class RouteGroup(ctypes.Structure):
                 ("nh_words", ctypes.c_int32), ("out", SpfOut)]
 
 
+class RouteDeltaPolicy(ctypes.Structure):
+    _fields_ = [("prev_applied", ctypes.c_void_p), ("prev_counter", ctypes.c_void_p),
+                ("next_applied", ctypes.c_void_p), ("next_counter", ctypes.c_void_p)]
+
+
+class RouteDeltaOut(ctypes.Structure):
+    _fields_ = [("capacity", ctypes.c_uint32), ("prefix", ctypes.c_void_p),
+                ("kind", ctypes.c_void_p), ("meta", ctypes.c_void_p),
+                ("metric", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("sel", ctypes.c_void_p), ("applied", ctypes.c_void_p),
+                ("counter", ctypes.c_void_p), ("header", ctypes.c_void_p)]
+
+
+def route_delta_workspace_bytes(num_prefixes):
+    """OGS_ROUTE_DELTA_WORKSPACE_BYTES of include/openr_gpu.h."""
+    return (num_prefixes + OGS_ROUTE_DELTA_TILE - 1) // OGS_ROUTE_DELTA_TILE * 528
+
+
 def load(path=None):
     lib = ctypes.CDLL(path or LIB_PATH)
     lib.ogs_version.restype = ctypes.c_char_p
@@ -84,6 +108,11 @@ def load(path=None):
     lib.ogs_get_option.restype = ctypes.c_int
     lib.ogs_option_name.argtypes = [ctypes.c_int32]
     lib.ogs_option_name.restype = ctypes.c_char_p
+    lib.ogs_route_delta.argtypes = [
+        ctypes.POINTER(SpfOut), ctypes.POINTER(SpfOut), ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.POINTER(RouteDeltaPolicy), ctypes.c_uint32, ctypes.c_int32,
+        ctypes.POINTER(RouteDeltaOut), ctypes.c_void_p, ctypes.c_void_p]
+    lib.ogs_route_delta.restype = ctypes.c_int
     # execution contexts (ABI 6): opaque handles
     lib.ogs_ctx_create.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
     lib.ogs_ctx_create.restype = ctypes.c_int

@@ -259,6 +259,12 @@ struct FlatTopology {
   bool hasZeroMetric{false};
   bool hasWideMetric{false};  // metric >= 2^32 (negative i32)
   uint64_t version{0};
+  // Stamp of the CSR's structure, taken when flat() builds it and kept by
+  // patchFlat (version moves on every patch): node ids and the link slots of
+  // every row are the same under one layout, so device records of two builds
+  // compare slot for slot, and tables that read the topology only through
+  // ids and counts (the prefix table, the compiled RibPolicy) stay valid.
+  uint64_t layout{0};
   int slotStride{0};  // ogs_graph.slot_stride of dSlot (0: none)
   int slotDegree{0};  // ogs_graph.slot_degree of dSlotEdges (0: none)
   // views into dBlock (one H2D per full upload); patches write in place
@@ -406,6 +412,10 @@ class LinkState {
   uint64_t flatBuilds() const { return flatBuilds_; }
   uint64_t flatPatches() const { return flatPatches_; }
   uint64_t edgesPatched() const { return edgesPatched_; }
+  // moves whenever updateAdjacencyDatabase reports linkAttributesChanged
+  // (adjLabel, weight, next-hop addresses): those alter materialised next
+  // hops without altering any route record
+  uint64_t attrEpoch() const { return attrEpoch_; }
 
  private:
   LinkPtr makeLink(const std::string& node, const Adjacency& adj) const;
@@ -443,6 +453,7 @@ class LinkState {
   uint64_t mutation_{0};
   mutable uint64_t flatBuilds_{0};
   uint64_t flatPatches_{0}, edgesPatched_{0};
+  uint64_t attrEpoch_{0};
   bool incrementalFlatten_{true};
 };
 
@@ -751,6 +762,24 @@ class SpfSolver {
   std::optional<DecisionRouteDb> buildRouteDb(
       const std::string& myNodeName, const AreaLinkStates& areaLinkStates,
       const PrefixState& prefixState);
+  // Decision::rebuildRoutes' full branch (Decision.cpp:912-927) in one call:
+  // the update Fib is handed (old.calculateUpdate(new), SpfSolver.cpp:21-56),
+  // with the solver's held RouteDb patched in place. When nothing but link /
+  // node attributes moved since the previous call (same source, topology
+  // layout and attribute epoch, PrefixState, flags, RibPolicy and statics;
+  // one area, next-hop sets of <= 4 words) the previous and the new record
+  // blocks are diffed on the device (ogs_route_delta) and only the changed
+  // records are downloaded and materialised; any other call runs
+  // buildRouteDb + calculateUpdate (counted in deltaFallbacks) and seeds the
+  // device state. Counters and getBestRoutesCache() move as one buildRouteDb
+  // moves them. nullopt (held db untouched) when myNodeName is in no area.
+  std::optional<DecisionRouteUpdate> rebuildRoutes(
+      const std::string& myNodeName, const AreaLinkStates& areaLinkStates,
+      const PrefixState& prefixState);
+  // == what buildRouteDb would return for the last rebuildRoutes' state
+  const DecisionRouteDb& routeDb() const { return heldDb_; }
+  uint64_t deltaBuilds() const { return deltaBuilds_; }
+  uint64_t deltaFallbacks() const { return deltaFallbacks_; }
   std::optional<RibUnicastEntry> createRouteForPrefixOrGetStaticRoute(
       const std::string& myNodeName, const AreaLinkStates& areaLinkStates,
       const PrefixState& prefixState, const std::string& prefix);
@@ -801,7 +830,32 @@ class SpfSolver {
   std::optional<DecisionRouteDb> buildRouteDbSingleArea(
       const std::string& myNodeName, const AreaLinkStates& areaLinkStates,
       const PrefixState& prefixState);
-  // single-area prefix table (packed, one H2D) cached on (ps, f) versions
+  // the SPF + route launch (+ RibPolicy pass) of one single-area source into
+  // `res`, shared by buildRouteDbSingleArea and rebuildRoutes
+  // launch shape of one single-area source: next-hop words, metric width,
+  // exactness and the flags word, stated once for every single-area path
+  struct UnitShape {
+    uint32_t s{0}, N{0}, flags{0};
+    int W{1};
+    bool wide{false}, exact{false};
+    size_t db{4};
+  };
+  UnitShape unitShape(const FlatTopology& f, uint32_t s) const;
+  struct SingleLaunch;
+  SingleLaunch launchSingleArea(const std::string& me, const LinkState& ls,
+                                const FlatTopology& f, const UnitShape& u, DeviceBuffer& res,
+                                uint16_t* applied, uint16_t* counter);
+  // rebuildRoutes: the launches of one build into delta block `slot`; the
+  // delta path (false: the key does not match, nothing was done); the seed
+  // of the device state after a full build
+  SingleLaunch launchDeltaSlot(int slot, const std::string& me, const LinkState& ls,
+                               const FlatTopology& f, const UnitShape& u);
+  bool rebuildRoutesFast(const std::string& me, const LinkState& ls, const std::string& area,
+                         const PrefixState& ps, DecisionRouteUpdate& update);
+  void seedDelta(const std::string& me, const LinkState& ls, const std::string& area,
+                 const PrefixState& ps);
+  // single-area prefix table (packed, one H2D) cached on the PrefixState
+  // version and the topology layout
   void prepareSingleArea(const FlatTopology& f, const PrefixState& ps,
                          const std::string& area);
   void routesFromSpfMemo(const std::string& me, const LinkState& ls,
@@ -835,6 +889,10 @@ class SpfSolver {
   std::unique_ptr<Impl> impl_;
   std::map<std::string, RibUnicastEntry> staticUnicastRoutes_;
   std::map<std::string, RouteSelectionResult> bestRoutesCache_;
+  // rebuildRoutes: the held RouteDb; stamps of the statics and of every
+  // write to bestRoutesCache_ by another entry point (part of the key)
+  DecisionRouteDb heldDb_;
+  uint64_t deltaBuilds_{0}, deltaFallbacks_{0}, staticsGen_{0}, selCacheGen_{0};
   // Per-prefix calls of Decision's incremental loop: the first call after a
   // PrefixState / topology change computes every prefix changed since the
   // last build or batch (PrefixState::changeLog) in ONE batch; the rest of
@@ -1091,6 +1149,9 @@ std::optional<RibUnicastEntry> materializeRouteAt(
     uint32_t p, uint32_t meta, uint64_t metric, const uint32_t* mask,
     size_t maskStride, int W, bool v4OverV6Nexthop, const RibPolicy* policy,
     uint16_t applied, uint16_t counter);
+
+// ogs_route_diff.adv_class / ogs_route_delta's adv_class of a prefix table
+std::vector<uint32_t> advClasses(const PrefixHostTable& table);
 
 // Changed records of many variants in the ogs_route_changes layout: variant
 // v owns records [offsets[v], offsets[v + 1]), record i = prefix index,

@@ -244,6 +244,7 @@ LinkState::LinkStateChange LinkState::updateAdjacencyDatabase(
     ++ni;
     ++oi;
   }
+  if (ch.linkAttributesChanged) ++attrEpoch_;
   if (!structural && incrementalFlatten_ && flat_ && !flatStale_) {
     patchFlat(name, touched, nodeFlagsChanged);
     if (ch.topologyChanged) clearSpfMemos();  // LinkState.cpp:635-638
@@ -257,7 +258,7 @@ void LinkState::patchFlat(const std::string& node, const std::vector<const Link*
                           bool nodeFlagsChanged) {
   FlatTopology& f = *flat_;
   ++mutation_;
-  f.version = nextVersionStamp();  // version-keyed caches (prefix tables, policies) rebuild
+  f.version = nextVersionStamp();  // version-keyed caches rebuild; f.layout stays
   ++flatPatches_;
   const uint32_t u = f.id.at(node);
   std::vector<uint32_t> dirty;
@@ -386,7 +387,7 @@ const FlatTopology& LinkState::flat() const {
   deviceSpf_.clear();
   deviceSpfBytes_ = 0;
   auto f = std::make_unique<FlatTopology>();
-  f->version = nextVersionStamp();
+  f->version = f->layout = nextVersionStamp();
   f->names.reserve(adjDbs_.size());
   f->id.reserve(adjDbs_.size());
   f->nodeFlags.reserve(adjDbs_.size());

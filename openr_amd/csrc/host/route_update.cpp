@@ -19,6 +19,39 @@
 
 namespace openr_amd {
 
+// Best-entry equality classes for the route diffs (ogs_route_diff.adv_class,
+// ogs_route_delta): per prefix, the list [entries as is, entries with the
+// drain override] of materialised best entries (weight cleared,
+// RibEntry.h:77), each numbered by the first equal one.
+std::vector<uint32_t> advClasses(const PrefixHostTable& table) {
+  std::vector<uint32_t> cls(std::max<size_t>(2 * table.advEntry.size(), 1), 0);
+  for (size_t p = 0; p + 1 < table.advOff.size(); ++p) {
+    const uint32_t a0 = table.advOff[p], k = table.advOff[p + 1] - a0;
+    std::vector<PrefixEntry> eff;
+    eff.reserve(2 * k);
+    for (int drained = 0; drained < 2; ++drained) {
+      for (uint32_t i = 0; i < k; ++i) {
+        PrefixEntry e = *table.advEntry[a0 + i];
+        e.weight = std::nullopt;
+        if (drained) e.metrics.drain_metric = 1;
+        eff.push_back(std::move(e));
+      }
+    }
+    for (uint32_t j = 0; j < 2 * k; ++j) {
+      uint32_t c = j;
+      for (uint32_t i = 0; i < j; ++i) {
+        if (eff[i] == eff[j]) {
+          c = i;
+          break;
+        }
+      }
+      const uint32_t i = j % k, drained = j / k;
+      cls[2 * (a0 + i) + drained] = c;
+    }
+  }
+  return cls;
+}
+
 LinkFailureSweep::LinkFailureSweep(
     const std::string& myNodeName, const LinkState& ls, const PrefixState& ps,
     const std::vector<std::vector<LinkDown>>& variants, bool enableV4,
@@ -91,36 +124,8 @@ LinkFailureSweep::LinkFailureSweep(
   dUnits_.upload(units.data(), units.size());
   dBaseUnit_.upload(&base, 1);
   dDead_.upload(dead_.data(), dead_.size());
-  // best-entry equality classes for the diff (ogs_route_diff.adv_class):
-  // per prefix, the list [entries as is, entries with the drain override]
-  // of materialised best entries (weight cleared, RibEntry.h:77), each
-  // numbered by the first equal one
   {
-    std::vector<uint32_t> cls(std::max<size_t>(2 * table_.advEntry.size(), 1), 0);
-    for (size_t p = 0; p + 1 < table_.advOff.size(); ++p) {
-      const uint32_t a0 = table_.advOff[p], k = table_.advOff[p + 1] - a0;
-      std::vector<PrefixEntry> eff;
-      eff.reserve(2 * k);
-      for (int drained = 0; drained < 2; ++drained) {
-        for (uint32_t i = 0; i < k; ++i) {
-          PrefixEntry e = *table_.advEntry[a0 + i];
-          e.weight = std::nullopt;
-          if (drained) e.metrics.drain_metric = 1;
-          eff.push_back(std::move(e));
-        }
-      }
-      for (uint32_t j = 0; j < 2 * k; ++j) {
-        uint32_t c = j;
-        for (uint32_t i = 0; i < j; ++i) {
-          if (eff[i] == eff[j]) {
-            c = i;
-            break;
-          }
-        }
-        const uint32_t i = j % k, drained = j / k;
-        cls[2 * (a0 + i) + drained] = c;
-      }
-    }
+    const std::vector<uint32_t> cls = advClasses(table_);
     dAdvClass_.upload(cls.data(), cls.size());
   }
   bDist_.resize(Sn * 4);

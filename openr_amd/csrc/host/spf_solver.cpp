@@ -346,7 +346,7 @@ struct SpfSolver::Impl {
   PinnedBuffer hTab;
   TableImage tabImg;
   const PrefixState* cachedPs{nullptr};
-  uint64_t cachedPsVersion{~0ull}, cachedTopoVersion{~0ull};
+  uint64_t cachedPsVersion{~0ull}, cachedTopoLayout{~0ull};
   const FlatTopology* cachedTopo{nullptr};
   PrefixHostTable table;
   // the unit (uploaded when the source changes) and the result block: one
@@ -359,6 +359,39 @@ struct SpfSolver::Impl {
   PinnedBuffer hSubTab, hSubRes;
   PrefixHostTable subTable;
   PolicyDevice policy;
+
+  // ---- rebuildRoutes: the previous and the next build's record blocks
+  // ping-pong on the device (res[cur] = the held db's records) ----
+  struct Delta {
+    bool valid{false};
+    int cur{0};
+    DeviceBuffer res[2], pol[2];  // ResultImage blocks; applied | counter
+    DeviceBuffer advClass, out, ws;
+    PinnedBuffer hOut, hSpf;
+    uint64_t advClassGen{0};  // table generation advClass was built for
+    uint32_t capacity{0};
+    // byte stride of one u16 policy column of P prefixes inside pol[i]
+    static size_t polColumn(size_t P) { return al256(std::max<size_t>(P, 1) * 2); }
+    // what the held state was computed for: a match takes the fast path
+    struct Key {
+      std::string me;
+      const FlatTopology* f{nullptr};
+      uint64_t layout{0}, attrEpoch{0};
+      const PrefixState* ps{nullptr};
+      uint64_t psVersion{0}, tableGen{0};
+      uint32_t flags{0}, N{0}, P{0};
+      int W{0};
+      const RibPolicy* policy{nullptr};
+      uint64_t policyUid{0}, staticsGen{0}, selCacheGen{0};
+      bool operator==(const Key& o) const {
+        return me == o.me && f == o.f && layout == o.layout && attrEpoch == o.attrEpoch &&
+            ps == o.ps && psVersion == o.psVersion && tableGen == o.tableGen &&
+            flags == o.flags && N == o.N && P == o.P && W == o.W && policy == o.policy &&
+            policyUid == o.policyUid && staticsGen == o.staticsGen &&
+            selCacheGen == o.selCacheGen;
+      }
+    } key;
+  } delta;
 
   // multi-area domain (buildRouteDbMultiArea): the areas' CSR as one graph
   // batch + the domain prefix table with per-entry area / node-name ids
@@ -398,6 +431,7 @@ void SpfSolver::updateStaticUnicastRoutes(
     const std::vector<std::string>& toDelete) {  // SpfSolver.cpp:109-137
   for (const auto& [p, e] : toUpdate) staticUnicastRoutes_[p] = e;
   for (const auto& p : toDelete) staticUnicastRoutes_.erase(p);
+  ++staticsGen_;
 }
 
 namespace {
@@ -428,19 +462,21 @@ NextHopThrift makeNh(const Link& l, const std::string& me, bool useV4,
 // links (per area) -- cached until the policy, table or topology changes --
 // and applied on the device (ogs_rib_policy_apply): next hops of weight 0
 // dropped in the device masks, statement choices left in D.applied /
-// D.counter (downloadPolicy).
+// D.counter (downloadPolicy), or in the caller's device columns when given.
 void runPolicyOnDevice(const RibPolicy& pol, const PrefixHostTable& table,
                        const ogs_prefix_table& pt,
                        const std::vector<std::pair<const FlatTopology*, uint32_t>>& src,
                        const std::string& me, int W, uint32_t* dMeta, uint32_t* dMask,
-                       PolicyDevice& D, void* stream) {
+                       PolicyDevice& D, void* stream, uint16_t* appliedOut = nullptr,
+                       uint16_t* counterOut = nullptr) {
   const size_t K = pol.numStatements();
   // applied / counter are u16 statement indexes with OGS_POLICY_NONE = none
   // (RibPolicy.cpp:231-249 walks any number of statements)
   if (K >= OGS_POLICY_NONE) throw std::domain_error("RibPolicy: more than 65,534 statements");
   const size_t P = table.prefixes.size(), A = src.size();
   PolicyDevice::Key key{pol.uid(), table.generation, &table, {}, W, me};
-  for (const auto& [f, s] : src) key.src.emplace_back(f, f->version, s);
+  // the tables read the source's slots' (area, neighbour) only: the layout
+  for (const auto& [f, s] : src) key.src.emplace_back(f, f->layout, s);
   if (!(key == D.key)) {
     D.chunks.clear();
     D.chunks.resize((K + 31) / 32);
@@ -501,7 +537,8 @@ void runPolicyOnDevice(const RibPolicy& pol, const PrefixHostTable& table,
   // RibPolicy.cpp:222-229)
   for (const auto& C : D.chunks) {
     ogsCheck(ogs_rib_policy_apply(&pt, &C.rp, int32_t(A), 1, W, dMeta, dMask,
-                                  D.applied.as<uint16_t>(), D.counter.as<uint16_t>(), stream),
+                                  appliedOut ? appliedOut : D.applied.as<uint16_t>(),
+                                  counterOut ? counterOut : D.counter.as<uint16_t>(), stream),
              "ogs_rib_policy_apply");
   }
 }
@@ -540,6 +577,25 @@ static bool noRouteReason(uint32_t meta) {
   if (meta & OGS_ROUTE_VALID) return false;
   const uint32_t r = (meta >> OGS_ROUTE_REASON_SHIFT) & 0xFu;
   return r == OGS_REASON_UNREACHABLE || r == OGS_REASON_NO_NEXTHOP;
+}
+
+// One prefix's getBestRoutesCache() entry from its record
+static void refreshSelection(std::map<std::string, RouteSelectionResult>& cache,
+                             const PrefixHostTable& pt, uint32_t p, uint32_t meta,
+                             uint32_t sel) {
+  const std::string& prefix = pt.prefixes[p];
+  if (!(meta & OGS_ROUTE_SELECTED)) {  // SpfSolver.cpp:247
+    cache.erase(prefix);
+    return;
+  }
+  RouteSelectionResult rs;
+  const uint32_t a0 = pt.advOff[p], a1 = pt.advOff[p + 1];
+  for (uint32_t a = a0; a < std::min(a1, a0 + 32); ++a) {
+    if (sel >> (a - a0) & 1u) rs.allNodeAreas.insert(pt.advKey[a]);
+  }
+  rs.bestNodeArea = pt.advKey[a0 + (meta >> OGS_ROUTE_BEST_SHIFT)];
+  rs.isBestNodeDrained = meta & OGS_ROUTE_DRAINED;
+  cache[prefix] = std::move(rs);
 }
 
 bool wideDistancesNeeded(const FlatTopology& f) {
@@ -822,9 +878,11 @@ void widenSpan(const void* src, size_t n, bool wide, std::vector<uint64_t>& v) {
 void SpfSolver::prepareSingleArea(const FlatTopology& f, const PrefixState& ps,
                                   const std::string& area) {
   Impl& I = *impl_;
-  // prefix table (cached on PrefixState / topology version): one packed H2D
+  // prefix table, one packed H2D, cached on the PrefixState version and the
+  // topology LAYOUT: the table reads the topology only through f.id and the
+  // node / edge counts (appendPrefixes), so an attribute-only patch keeps it
   if (I.cachedPs == &ps && I.cachedPsVersion == ps.version() && I.cachedTopo == &f &&
-      I.cachedTopoVersion == f.version) {
+      I.cachedTopoLayout == f.layout) {
     return;
   }
   HostBatch hb;
@@ -838,7 +896,7 @@ void SpfSolver::prepareSingleArea(const FlatTopology& f, const PrefixState& ps,
   I.cachedPs = &ps;
   I.cachedPsVersion = ps.version();
   I.cachedTopo = &f;
-  I.cachedTopoVersion = f.version;
+  I.cachedTopoLayout = f.layout;
 }
 
 std::optional<DecisionRouteDb> SpfSolver::buildRouteDb(
@@ -846,6 +904,7 @@ std::optional<DecisionRouteDb> SpfSolver::buildRouteDb(
   bool exists = false;  // SpfSolver.cpp:318-324
   for (const auto& [_, l] : als) exists |= l.hasNode(me);
   if (!exists) return std::nullopt;
+  ++selCacheGen_;  // the selection cache is rebuilt: rebuildRoutes' key
   const auto t0 = std::chrono::steady_clock::now();
   if (!quietStats_) {
     addStatValue("decision.route_build_runs", 1, StatType::COUNT);  // SpfSolver.cpp:327
@@ -866,15 +925,388 @@ std::optional<DecisionRouteDb> SpfSolver::buildRouteDb(
   return db;
 }
 
+SpfSolver::UnitShape SpfSolver::unitShape(const FlatTopology& f, uint32_t s) const {
+  UnitShape u;
+  u.s = s;
+  u.N = uint32_t(f.names.size());
+  u.W = std::max(1, ogs_nh_words_for_degree(int(f.rowPtr[s + 1] - f.rowPtr[s])));
+  // zero / negative link metrics: the reference's extraction order replayed
+  // on the device (spf_exact.hip), 64-bit distances
+  u.exact = f.hasZeroMetric || f.hasWideMetric;
+  u.wide = u.exact || wideDistancesNeeded(f);
+  u.db = u.wide ? 8 : 4;
+  u.flags = (enableV4_ ? OGS_F_ENABLE_V4 : 0u) | (v4OverV6Nexthop_ ? OGS_F_V4_OVER_V6 : 0u) |
+      (enableBestRouteSelection_ ? OGS_F_BEST_ROUTE_SELECTION : 0u) |
+      (u.wide ? OGS_F_WIDE_METRIC : 0u) | (u.exact ? OGS_F_EXACT_ORDER : 0u);
+  return u;
+}
+
+struct SpfSolver::SingleLaunch {
+  uint32_t P{0};
+  ResultImage L;
+  ogs_prefix_table pt{};
+  LinkState::DeviceSpf* memo{nullptr};
+  const RibPolicy* policy{nullptr};  // the active policy, applied when P > 0
+};
+
+// The launches of one single-area build after prepareSingleArea: the records
+// of (f, me) into `res` (ResultImage layout), the RibPolicy pass over them
+// with its statement choices in applied / counter (nullptr: Impl::policy's).
+// Nothing is downloaded and nothing waits.
+SpfSolver::SingleLaunch SpfSolver::launchSingleArea(const std::string& me, const LinkState& ls,
+                                                    const FlatTopology& f, const UnitShape& u,
+                                                    DeviceBuffer& res, uint16_t* applied,
+                                                    uint16_t* counter) {
+  Impl& I = *impl_;
+  SingleLaunch r;
+  const uint32_t s = u.s, N = u.N;
+  const int W = u.W;
+  const bool exact = u.exact;
+  const uint32_t P = r.P = uint32_t(I.table.prefixes.size());
+  if (I.unitSrc != s) {
+    const ogs_unit unit{0, s};
+    I.unit.upload(&unit, 1);
+    I.unitSrc = s;
+  }
+  const ResultImage L(N, P, W, u.db);
+  r.L = L;
+  res.resize(L.end);
+
+  const ogs_graph g = singleGraph(f, devAt<uint32_t>(I.tab, I.tabImg.desc));
+  const ogs_prefix_table pt = r.pt = I.tabImg.view(I.tab);
+  ogs_spf_out out{};
+  out.meta = devAt<uint32_t>(res, L.meta);
+  out.metric = devAt<void>(res, L.metric);
+  out.mask = devAt<uint32_t>(res, L.mask);
+  out.sel = devAt<uint32_t>(res, L.sel);
+  // SPF memo (LinkState::getSpfResult, LinkState.cpp:705-715): the
+  // LinkState's device rows of this source -> the route pass alone, no SPF
+  // relaunch (ogs_routes_from_spf); else ONE fused launch writes the SPF
+  // into a new memo slot and the records into res
+  LinkState::DeviceSpf* memo = ls.findDeviceSpf(s, true, N, W, u.db, exact);
+  if (memo) {
+    if (P) {
+      ogsCheck(ogs_routes_from_spf(&g, &pt, I.unit.as<ogs_unit>(), 1, memo->dist(),
+                                   memo->nh(), exact ? memo->reach() : nullptr, u.flags, W,
+                                   &out, nullptr),
+               "ogs_routes_from_spf");
+    }
+  } else {
+    LinkState::DeviceSpf& slot = ls.newDeviceSpf(s, true, N, W, u.db, exact);
+    out.dist = slot.dist();
+    out.nh = slot.nh();
+    out.reached = exact ? slot.reach() : nullptr;
+    ogsCheck(ogs_spf_routes(&g, P ? &pt : nullptr, I.unit.as<ogs_unit>(), 1,
+                            u.flags, W, &out, nullptr),
+             "ogs_spf_routes");
+    ls.commitDeviceSpf(slot, me, true);
+    memo = &slot;
+  }
+  r.memo = memo;
+  r.policy = (ribPolicy_ && ribPolicy_->isActive()) ? ribPolicy_ : nullptr;
+  if (r.policy && P) {
+    runPolicyOnDevice(*r.policy, I.table, pt, {{&f, s}}, me, W, out.meta, out.mask,
+                      I.policy, nullptr, applied, counter);
+  }
+  return r;
+}
+
+// Byte layout of ogs_route_delta's outputs in one block, arrays strided by
+// the capacity C: header | prefix | kind | meta | sel | metric | mask [W][C] |
+// applied | counter.
+struct DeltaImage {
+  size_t header{0}, prefix{0}, kind{0}, meta{0}, sel{0}, metric{0}, mask{0}, applied{0},
+      counter{0}, end{0};
+  DeltaImage(uint32_t C, int W, size_t db) {
+    prefix = al256(16);
+    kind = prefix + al256(size_t(C) * 4);
+    meta = kind + al256(size_t(C) * 4);
+    sel = meta + al256(size_t(C) * 4);
+    metric = sel + al256(size_t(C) * 4);
+    mask = metric + al256(size_t(C) * db);
+    applied = mask + al256(size_t(C) * W * 4);
+    counter = applied + al256(size_t(C) * 2);
+    end = counter + al256(size_t(C) * 2);
+  }
+};
+
+std::optional<DecisionRouteUpdate> SpfSolver::rebuildRoutes(
+    const std::string& me, const AreaLinkStates& als, const PrefixState& ps) {
+  bool exists = false;  // SpfSolver.cpp:318-324
+  for (const auto& [_, l] : als) exists |= l.hasNode(me);
+  if (!exists) return std::nullopt;
+  DecisionRouteUpdate update;
+  if (als.size() == 1) {
+    const auto& [area, ls] = *als.begin();
+    if (rebuildRoutesFast(me, ls, area, ps, update)) {
+      ++deltaBuilds_;
+      return update;
+    }
+  }
+  // first call, key mismatch, several areas or wide next-hop sets: the full
+  // build and the host diff, then the device state for the next call
+  ++deltaFallbacks_;
+  impl_->delta.valid = false;
+  auto db = buildRouteDb(me, als, ps);
+  if (!db) return std::nullopt;
+  update = heldDb_.calculateUpdate(*db);
+  heldDb_ = std::move(*db);
+  if (als.size() == 1) {
+    const auto& [area, ls] = *als.begin();
+    seedDelta(me, ls, area, ps);
+  }
+  return update;
+}
+
+SpfSolver::SingleLaunch SpfSolver::launchDeltaSlot(int slot, const std::string& me,
+                                                   const LinkState& ls, const FlatTopology& f,
+                                                   const UnitShape& u) {
+  Impl& I = *impl_;
+  Impl::Delta& D = I.delta;
+  uint16_t *applied = nullptr, *counter = nullptr;
+  if (ribPolicy_ && ribPolicy_->isActive()) {
+    const size_t polCol = D.polColumn(I.table.prefixes.size());
+    D.pol[slot].resize(2 * polCol);
+    applied = devAt<uint16_t>(D.pol[slot], 0);
+    counter = devAt<uint16_t>(D.pol[slot], polCol);
+  }
+  return launchSingleArea(me, ls, f, u, D.res[slot], applied, counter);
+}
+
+// After a full build: the same records once more into the current delta
+// block (SPF memo hit: the route pass alone) and the key they were built for.
+// Sources of more than 4 next-hop words are left unseeded: always a fallback.
+void SpfSolver::seedDelta(const std::string& me, const LinkState& ls, const std::string& area,
+                          const PrefixState& ps) {
+  Impl& I = *impl_;
+  Impl::Delta& D = I.delta;
+  const FlatTopology& f = ls.flatOnDevice();
+  const UnitShape shape = unitShape(f, f.id.at(me));
+  if (shape.W > 4) return;
+  prepareSingleArea(f, ps, area);
+  const SingleLaunch sl = launchDeltaSlot(D.cur, me, ls, f, shape);
+  if (D.advClassGen != I.table.generation || !D.advClass.get()) {
+    const std::vector<uint32_t> cls = advClasses(I.table);
+    D.advClass.upload(cls.data(), cls.size());
+    D.advClassGen = I.table.generation;
+  }
+  D.key = Impl::Delta::Key{me, &f, f.layout, ls.attrEpoch(), &ps, ps.version(),
+                           I.table.generation, shape.flags, shape.N, sl.P, shape.W, sl.policy,
+                           sl.policy ? sl.policy->uid() : 0, staticsGen_, selCacheGen_};
+  D.valid = true;
+}
+
+// The delta path of rebuildRoutes: true when the held state's key matches
+// (`update` is filled, the held db and the selection cache are patched).
+bool SpfSolver::rebuildRoutesFast(const std::string& me, const LinkState& ls,
+                                  const std::string& area, const PrefixState& ps,
+                                  DecisionRouteUpdate& update) {
+  Impl& I = *impl_;
+  Impl::Delta& D = I.delta;
+  if (!D.valid) return false;
+  const auto t0 = std::chrono::steady_clock::now();
+  const FlatTopology& f = ls.flatOnDevice();
+  const auto sIt = f.id.find(me);
+  if (sIt == f.id.end()) return false;
+  const uint32_t s = sIt->second;
+  const UnitShape shape = unitShape(f, s);
+  const int W = shape.W;
+  const bool exact = shape.exact;
+  const RibPolicy* policy = (ribPolicy_ && ribPolicy_->isActive()) ? ribPolicy_ : nullptr;
+  // the table (generation, size) is the held one when ps and the layout are:
+  // compared before prepareSingleArea could rebuild it
+  const Impl::Delta::Key key{me, &f, f.layout, ls.attrEpoch(), &ps, ps.version(),
+                             I.table.generation, shape.flags, shape.N, D.key.P, W, policy,
+                             policy ? policy->uid() : 0, staticsGen_, selCacheGen_};
+  if (!(key == D.key) || I.cachedPs != &ps || I.cachedPsVersion != ps.version() ||
+      I.cachedTopo != &f || I.cachedTopoLayout != f.layout) {
+    return false;
+  }
+  if (!quietStats_) {  // as buildRouteDb (SpfSolver.cpp:327, 334-339)
+    addStatValue("decision.route_build_runs", 1, StatType::COUNT);
+    addStatValue("decision.get_route_for_prefix", double(ps.prefixes().size()),
+                 StatType::COUNT);
+  }
+  prepareSingleArea(f, ps, area);  // current by the checks above
+  addStatValue("decision.gpu.prepare_ms", msSince(t0), StatType::AVG);
+  const auto tLaunch = std::chrono::steady_clock::now();
+
+  const uint32_t P = key.P;
+  const int nxt = 1 - D.cur;
+  const SingleLaunch sl = launchDeltaSlot(nxt, me, ls, f, shape);
+  addStatValue("decision.gpu.launch_ms", msSince(tLaunch), StatType::AVG);
+  const auto tDelta = std::chrono::steady_clock::now();
+
+  // ---- the device diff: header first, then the changed records only --------
+  const ResultImage& L = sl.L;
+  auto side = [&](int i) {
+    ogs_spf_out o{};
+    o.meta = devAt<uint32_t>(D.res[i], L.meta);
+    o.metric = devAt<void>(D.res[i], L.metric);
+    o.mask = devAt<uint32_t>(D.res[i], L.mask);
+    o.sel = devAt<uint32_t>(D.res[i], L.sel);
+    return o;
+  };
+  const ogs_spf_out prev = side(D.cur), next = side(nxt);
+  ogs_route_delta_policy cols{};
+  if (policy) {
+    const size_t polCol = D.polColumn(P);
+    cols = ogs_route_delta_policy{devAt<uint16_t>(D.pol[D.cur], 0),
+                                  devAt<uint16_t>(D.pol[D.cur], polCol),
+                                  devAt<uint16_t>(D.pol[nxt], 0),
+                                  devAt<uint16_t>(D.pol[nxt], polCol)};
+  }
+  D.ws.resize(std::max<size_t>(OGS_ROUTE_DELTA_WORKSPACE_BYTES(P), 16));
+  uint32_t total = 0, noRoute = 0;
+  constexpr uint32_t kFloor = 2048;            // records: the smallest block
+  constexpr size_t kOneCopy = size_t(128) << 10;  // blocks up to this: one D2H
+  if (D.capacity < kFloor) D.capacity = kFloor;
+  D.hOut.resize(DeltaImage(D.capacity, W, shape.db).end);  // also when P == 0
+  for (int attempt = 0; P && attempt < 2; ++attempt) {
+    const uint32_t C = D.capacity;
+    const DeltaImage M(C, W, shape.db);
+    D.out.resize(M.end);
+    D.hOut.resize(M.end);
+    ogs_route_delta_out o{};
+    o.capacity = C;
+    o.header = devAt<uint32_t>(D.out, M.header);
+    o.prefix = devAt<uint32_t>(D.out, M.prefix);
+    o.kind = devAt<uint32_t>(D.out, M.kind);
+    o.meta = devAt<uint32_t>(D.out, M.meta);
+    o.sel = devAt<uint32_t>(D.out, M.sel);
+    o.metric = devAt<void>(D.out, M.metric);
+    o.mask = devAt<uint32_t>(D.out, M.mask);
+    o.applied = devAt<uint16_t>(D.out, M.applied);
+    o.counter = devAt<uint16_t>(D.out, M.counter);
+    ogsCheck(ogs_route_delta(&prev, &next, int32_t(P), sl.pt.adv_off, D.advClass.as<uint32_t>(),
+                             policy ? &cols : nullptr, shape.wide ? OGS_F_WIDE_METRIC : 0u, W, &o,
+                             D.ws.get(), nullptr),
+             "ogs_route_delta");
+    auto d2h = [&](size_t off, size_t bytes) {
+      ogsCheck(ogs_memcpy_d2h(D.hOut.at<char>(off), devAt<char>(D.out, off), bytes, nullptr),
+               "ogs_memcpy_d2h");
+    };
+    const bool oneCopy = M.end <= kOneCopy;
+    d2h(M.header, oneCopy ? M.end : 16);
+    ogsCheck(ogs_stream_sync(nullptr), "ogs_stream_sync");
+    const uint32_t* h = D.hOut.at<uint32_t>(M.header);
+    total = h[0];
+    noRoute = h[3];
+    if (total > C) {  // a change past the block: grow and gather again
+      D.capacity = total + total / 4;
+      continue;
+    }
+    if (!oneCopy && total) {
+      for (size_t off : {M.prefix, M.kind, M.meta, M.sel}) d2h(off, size_t(total) * 4);
+      d2h(M.metric, size_t(total) * shape.db);
+      for (int w = 0; w < W; ++w) d2h(M.mask + size_t(w) * C * 4, size_t(total) * 4);
+      if (policy) {
+        d2h(M.applied, size_t(total) * 2);
+        d2h(M.counter, size_t(total) * 2);
+      }
+      ogsCheck(ogs_stream_sync(nullptr), "ogs_stream_sync");
+    }
+    break;
+  }
+  // node-label routes read the SPF rows (N nodes: host work as in a build)
+  std::vector<uint64_t> dist;
+  const uint32_t N = shape.N;
+  if (enableNodeSegmentLabel_) {
+    D.hSpf.resize(L.meta);
+    ogsCheck(ogs_memcpy_d2h(D.hSpf.at<char>(L.dist), sl.memo->dist(), L.nh - L.dist, nullptr),
+             "ogs_memcpy_d2h");
+    ogsCheck(ogs_memcpy_d2h(D.hSpf.at<char>(L.nh), sl.memo->nh(), L.reach - L.nh, nullptr),
+             "ogs_memcpy_d2h");
+    if (exact) {
+      ogsCheck(ogs_memcpy_d2h(D.hSpf.at<char>(L.reach), sl.memo->reach(), L.meta - L.reach,
+                              nullptr),
+               "ogs_memcpy_d2h");
+    }
+    ogsCheck(ogs_stream_sync(nullptr), "ogs_stream_sync");
+    widenSpan(D.hSpf.at<void>(L.dist), N, shape.wide, dist);
+  }
+  addStatValue("decision.gpu.delta_ms", msSince(tDelta), StatType::AVG);
+  const auto tMat = std::chrono::steady_clock::now();
+
+  // ---- patch the held db and the selection cache from the records ----------
+  const DeltaImage M(D.capacity, W, shape.db);
+  const uint32_t* rPrefix = D.hOut.at<uint32_t>(M.prefix);
+  const uint32_t* rKind = D.hOut.at<uint32_t>(M.kind);
+  const uint32_t* rMeta = D.hOut.at<uint32_t>(M.meta);
+  const uint32_t* rSel = D.hOut.at<uint32_t>(M.sel);
+  const uint32_t* rMask = D.hOut.at<uint32_t>(M.mask);
+  const uint16_t* rApplied = D.hOut.at<uint16_t>(M.applied);
+  const uint16_t* rCounter = D.hOut.at<uint16_t>(M.counter);
+  const uint32_t rb = f.rowPtr[s];
+  auto& held = heldDb_.unicastRoutes;
+  for (uint32_t i = 0; i < total; ++i) {
+    const uint32_t p = rPrefix[i], meta = rMeta[i];
+    refreshSelection(bestRoutesCache_, I.table, p, meta, rSel[i]);
+    if (!(rKind[i] & OGS_DELTA_ROUTE)) continue;
+    const std::string& prefix = I.table.prefixes[p];
+    std::optional<RibUnicastEntry> e;
+    if (meta & OGS_ROUTE_VALID) {
+      uint64_t metric;
+      if (shape.wide) {
+        metric = D.hOut.at<uint64_t>(M.metric)[i];
+      } else {
+        const uint32_t m = D.hOut.at<uint32_t>(M.metric)[i];
+        metric = m == 0xFFFFFFFFu ? ~0ull : m;
+      }
+      e = materializeRouteAt(f, rb, me, I.table, p, meta, metric, &rMask[i], D.capacity, W,
+                             v4OverV6Nexthop_, policy, policy ? rApplied[i] : OGS_POLICY_NONE,
+                             policy ? rCounter[i] : OGS_POLICY_NONE);
+    } else if (auto st = staticUnicastRoutes_.find(prefix); st != staticUnicastRoutes_.end()) {
+      e = st->second;  // SpfSolver.cpp:343-349: the static route shows again
+      if (policy) policy->applyAction(*e);
+    }
+    auto it = held.find(prefix);
+    if (!e) {
+      if (it != held.end()) {
+        update.unicastRoutesToDelete.push_back(prefix);
+        held.erase(it);
+      }
+    } else if (it == held.end()) {
+      update.unicastRoutesToUpdate.emplace(prefix, *e);
+      held.emplace(prefix, std::move(*e));
+    } else if (it->second != *e) {
+      update.unicastRoutesToUpdate.emplace(prefix, *e);
+      it->second = std::move(*e);
+    }
+  }
+  // calculateUpdate lists deletions in the old map's (prefix) order
+  std::sort(update.unicastRoutesToDelete.begin(), update.unicastRoutesToDelete.end());
+  if (noRoute) addStatValue("decision.no_route_to_prefix", double(noRoute), StatType::COUNT);
+  if (enableNodeSegmentLabel_) {  // SpfSolver.cpp:354-445, diffed as maps
+    LabelRoutes labelToNode;
+    addNodeLabelRoutes(ls, f, area, me, dist.data(), D.hSpf.at<uint32_t>(L.nh), N, W,
+                       labelToNode, exact ? D.hSpf.at<uint32_t>(L.reach) : nullptr);
+    DecisionRouteDb was, now;
+    was.mplsRoutes = std::move(heldDb_.mplsRoutes);
+    for (auto& [label, ne] : labelToNode) now.mplsRoutes.emplace(label, std::move(ne.second));
+    DecisionRouteUpdate mpls = was.calculateUpdate(now);
+    update.mplsRoutesToUpdate = std::move(mpls.mplsRoutesToUpdate);
+    update.mplsRoutesToDelete = std::move(mpls.mplsRoutesToDelete);
+    heldDb_.mplsRoutes = std::move(now.mplsRoutes);
+  }
+  addStatValue("decision.gpu.materialize_ms", msSince(tMat), StatType::AVG);
+  D.cur = nxt;
+  // every change so far is in this build (as buildRouteDb)
+  ps.trackChanges();
+  incPs_ = &ps;
+  incLogCursor_ = ps.changeLogEnd();
+  if (!quietStats_) {
+    addStatValue("decision.route_build_ms", msSince(t0), StatType::AVG);  // SpfSolver.cpp:450
+  }
+  return true;
+}
+
 std::optional<DecisionRouteDb> SpfSolver::buildRouteDbSingleArea(
     const std::string& me, const AreaLinkStates& als, const PrefixState& ps) {
   const auto tPrep = std::chrono::steady_clock::now();
   std::string area;
   const LinkState& ls = singleArea(als, area);
   const FlatTopology& f = ls.flatOnDevice();
-  // zero / negative link metrics: the reference's extraction order replayed
-  // on the device (spf_exact.hip), 64-bit distances
-  const bool exact = f.hasZeroMetric || f.hasWideMetric;
   Impl& I = *impl_;
   prepareSingleArea(f, ps, area);
   // flatten / device CSR + prefix table when stale (cached otherwise)
@@ -882,63 +1314,17 @@ std::optional<DecisionRouteDb> SpfSolver::buildRouteDbSingleArea(
   const auto tLaunch = std::chrono::steady_clock::now();
 
   // ---- launch the fused kernel for (topology, me) -------------------------
-  const uint32_t s = f.id.at(me);
-  const uint32_t N = uint32_t(f.names.size());
-  const uint32_t P = uint32_t(I.table.prefixes.size());
-  const int degree = int(f.rowPtr[s + 1] - f.rowPtr[s]);
-  const int W = std::max(1, ogs_nh_words_for_degree(degree));
-  const bool wide = exact || wideDistancesNeeded(f);
-  const size_t db = wide ? 8 : 4;
-  if (I.unitSrc != s) {
-    const ogs_unit u{0, s};
-    I.unit.upload(&u, 1);
-    I.unitSrc = s;
-  }
-  const ResultImage L(N, P, W, db);
-  I.res.resize(L.end);
+  const UnitShape shape = unitShape(f, f.id.at(me));
+  const SingleLaunch sl = launchSingleArea(me, ls, f, shape, I.res, nullptr, nullptr);
+  const uint32_t N = shape.N, P = sl.P;
+  const int W = shape.W;
+  const bool wide = shape.wide, exact = shape.exact;
+  const ResultImage& L = sl.L;
+  LinkState::DeviceSpf* memo = sl.memo;
+  const RibPolicy* policy = sl.policy;
   I.hRes.resize(L.end);
-
-  const ogs_graph g = singleGraph(f, devAt<uint32_t>(I.tab, I.tabImg.desc));
-  const ogs_prefix_table pt = I.tabImg.view(I.tab);
-  ogs_spf_out out{};
-  out.meta = devAt<uint32_t>(I.res, L.meta);
-  out.metric = devAt<void>(I.res, L.metric);
-  out.mask = devAt<uint32_t>(I.res, L.mask);
-  out.sel = devAt<uint32_t>(I.res, L.sel);
-  const uint32_t flags = (enableV4_ ? OGS_F_ENABLE_V4 : 0u) |
-      (v4OverV6Nexthop_ ? OGS_F_V4_OVER_V6 : 0u) |
-      (enableBestRouteSelection_ ? OGS_F_BEST_ROUTE_SELECTION : 0u) |
-      (wide ? OGS_F_WIDE_METRIC : 0u) | (exact ? OGS_F_EXACT_ORDER : 0u);
-  // SPF memo (LinkState::getSpfResult, LinkState.cpp:705-715): the
-  // LinkState's device rows of this source -> the route pass alone, no SPF
-  // relaunch (ogs_routes_from_spf); else ONE fused launch writes the SPF
-  // into a new memo slot and the records into res
-  LinkState::DeviceSpf* memo = ls.findDeviceSpf(s, true, N, W, db, exact);
-  if (memo) {
-    if (P) {
-      ogsCheck(ogs_routes_from_spf(&g, &pt, I.unit.as<ogs_unit>(), 1, memo->dist(),
-                                   memo->nh(), exact ? memo->reach() : nullptr, flags, W, &out,
-                                   nullptr),
-               "ogs_routes_from_spf");
-    }
-  } else {
-    LinkState::DeviceSpf& slot = ls.newDeviceSpf(s, true, N, W, db, exact);
-    out.dist = slot.dist();
-    out.nh = slot.nh();
-    out.reached = exact ? slot.reach() : nullptr;
-    ogsCheck(ogs_spf_routes(&g, P ? &pt : nullptr, I.unit.as<ogs_unit>(), 1,
-                            flags, W, &out, nullptr),
-             "ogs_spf_routes");
-    ls.commitDeviceSpf(slot, me, true);
-    memo = &slot;
-  }
-  const RibPolicy* policy = (ribPolicy_ && ribPolicy_->isActive()) ? ribPolicy_ : nullptr;
   std::vector<uint16_t> applied, counter;
-  if (policy && P) {
-    runPolicyOnDevice(*policy, I.table, pt, {{&f, s}}, me, W, out.meta, out.mask,
-                      I.policy, nullptr);
-    downloadPolicy(I.policy, P, applied, counter);
-  }
+  if (policy && P) downloadPolicy(I.policy, P, applied, counter);
   // ONE D2H of the records (+ the SPF rows when node-label routes read them)
   ogsCheck(ogs_memcpy_d2h(I.hRes.at<char>(L.meta), devAt<char>(I.res, L.meta),
                           L.end - L.meta, nullptr),
@@ -996,17 +1382,11 @@ void SpfSolver::routesFromSpfMemo(const std::string& me, const LinkState& ls,
   Impl& I = *impl_;
   const auto tIn = std::chrono::steady_clock::now();
   const FlatTopology& f = ls.flatOnDevice();
-  const bool exact = f.hasZeroMetric || f.hasWideMetric;
-  const uint32_t s = f.id.at(me);
-  const uint32_t N = uint32_t(f.names.size());
-  const int degree = int(f.rowPtr[s + 1] - f.rowPtr[s]);
-  const int W = std::max(1, ogs_nh_words_for_degree(degree));
-  const bool wide = exact || wideDistancesNeeded(f);
-  const size_t db = wide ? 8 : 4;
-  const uint32_t flags = (enableV4_ ? OGS_F_ENABLE_V4 : 0u) |
-      (v4OverV6Nexthop_ ? OGS_F_V4_OVER_V6 : 0u) |
-      (enableBestRouteSelection_ ? OGS_F_BEST_ROUTE_SELECTION : 0u) |
-      (wide ? OGS_F_WIDE_METRIC : 0u) | (exact ? OGS_F_EXACT_ORDER : 0u);
+  const UnitShape shape = unitShape(f, f.id.at(me));
+  const uint32_t s = shape.s, N = shape.N, flags = shape.flags;
+  const int W = shape.W;
+  const bool wide = shape.wide, exact = shape.exact;
+  const size_t db = shape.db;
   if (I.unitSrc != s) {
     const ogs_unit u{0, s};
     I.unit.upload(&u, 1);
@@ -1071,18 +1451,7 @@ void SpfSolver::routesFromSpfMemo(const std::string& me, const LinkState& ls,
   for (uint32_t p = 0; p < np; ++p) {
     const std::string& prefix = st.prefixes[p];
     noRoute += noRouteReason(meta[p]);
-    if (meta[p] & OGS_ROUTE_SELECTED) {  // SpfSolver.cpp:247
-      RouteSelectionResult rs;
-      const uint32_t a0 = st.advOff[p], a1 = st.advOff[p + 1];
-      for (uint32_t a = a0; a < std::min(a1, a0 + 32); ++a) {
-        if (sel[p] >> (a - a0) & 1u) rs.allNodeAreas.insert(st.advKey[a]);
-      }
-      rs.bestNodeArea = st.advKey[a0 + (meta[p] >> OGS_ROUTE_BEST_SHIFT)];
-      rs.isBestNodeDrained = meta[p] & OGS_ROUTE_DRAINED;
-      bestRoutesCache_[prefix] = std::move(rs);
-    } else {
-      bestRoutesCache_.erase(prefix);
-    }
+    refreshSelection(bestRoutesCache_, st, p, meta[p], sel[p]);
     out[prefix] = materializeRoute(f, me, st, p, meta[p], metric[p], &mask[p], np, W,
                                    v4OverV6Nexthop_, nullptr, OGS_POLICY_NONE,
                                    OGS_POLICY_NONE);
@@ -1205,6 +1574,7 @@ void SpfSolver::prepareMultiArea(const AreaLinkStates& als, const PrefixState& p
 DecisionRouteDb SpfSolver::materializeMultiArea(const std::string& me,
                                                 const AreaLinkStates& als,
                                                 const MultiAreaResult& R) {
+  ++selCacheGen_;
   Impl::MultiArea& M = impl_->ma;
   const uint32_t A = uint32_t(als.size());
   const int W = R.W;
@@ -1470,6 +1840,7 @@ DecisionRouteDb SpfSolver::downloadMultiArea(const std::string& me,
 std::optional<RibUnicastEntry> SpfSolver::createRouteForPrefixOrGetStaticRoute(
     const std::string& me, const AreaLinkStates& als, const PrefixState& ps,
     const std::string& prefix) {  // SpfSolver.cpp:139-158
+  ++selCacheGen_;
   addStatValue("decision.get_route_for_prefix", 1.0, StatType::COUNT);  // :166
   std::vector<std::pair<const FlatTopology*, uint64_t>> topo;
   for (const auto& [_, l] : als) {
@@ -1550,6 +1921,7 @@ std::map<std::string, std::optional<RibUnicastEntry>> SpfSolver::createRoutesFor
     const std::string& me, const AreaLinkStates& als, const PrefixState& ps,
     const std::set<std::string>& prefixes) {
   // SpfSolver.cpp:166: one createRouteForPrefix per asked prefix
+  ++selCacheGen_;
   addStatValue("decision.get_route_for_prefix", double(prefixes.size()), StatType::COUNT);
   auto out = computeRoutes(me, als, ps, prefixes);
   for (auto& [prefix, route] : out) {  // static routes as the fallback

@@ -10,6 +10,9 @@
 // engine's own split of a single-area build: decision.gpu.prepare_ms (CSR
 // flatten and uploads when stale), decision.gpu.launch_ms (kernels to stream
 // sync, D2H included) and decision.gpu.materialize_ms (host RouteDb).
+// SpfSolver::rebuildRoutes' delta path adds decision.gpu.delta_ms
+// (ogs_route_delta, the D2H of the changed records and the stream sync, which
+// also waits for the launches launch_ms only enqueued).
 #include <mutex>
 
 #include "decision.h"

@@ -456,6 +456,46 @@ int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
   return e == hipSuccess ? OGS_OK : hipFail(e, "route changes gather");
 }
 
+int ogs_route_delta(const ogs_spf_out* prev, const ogs_spf_out* next, int32_t num_prefixes,
+                    const uint32_t* adv_off, const uint32_t* adv_class,
+                    const ogs_route_delta_policy* policy, uint32_t flags, int32_t nh_words,
+                    const ogs_route_delta_out* out, void* workspace, void* stream) {
+  if (num_prefixes < 0) return fail(OGS_E_INVALID, "num_prefixes < 0");
+  if (num_prefixes == 0) return OGS_OK;
+  if (!prev || !next || !out || !workspace) {
+    return fail(OGS_E_INVALID, "prev/next/out/workspace is NULL");
+  }
+  for (const ogs_spf_out* r : {prev, next}) {
+    if (!r->meta || !r->metric || !r->mask || !r->sel) {
+      return fail(OGS_E_INVALID, "records need meta, metric, mask and sel");
+    }
+  }
+  if ((adv_off == nullptr) != (adv_class == nullptr)) {
+    return fail(OGS_E_INVALID, "adv_off and adv_class go together");
+  }
+  if (policy && !policy->prev_applied && !policy->prev_counter && !policy->next_applied &&
+      !policy->next_counter) {
+    policy = nullptr;
+  }
+  if (policy && (!policy->prev_applied || !policy->prev_counter || !policy->next_applied ||
+                 !policy->next_counter)) {
+    return fail(OGS_E_INVALID, "policy columns of one side only");
+  }
+  if (flags & ~OGS_F_WIDE_METRIC) return fail(OGS_E_INVALID, "flags: OGS_F_WIDE_METRIC only");
+  if (nh_words != 1 && nh_words != 2 && nh_words != 4) {
+    return fail(OGS_E_UNSUPPORTED, "nh_words must be 1, 2 or 4");
+  }
+  if (!out->header) return fail(OGS_E_INVALID, "header is NULL");
+  if (out->capacity && (!out->prefix || !out->kind || !out->meta || !out->metric ||
+                        !out->mask || !out->sel || (policy && (!out->applied || !out->counter)))) {
+    return fail(OGS_E_INVALID, "delta record arrays are NULL");
+  }
+  hipError_t e = ogs::launch_route_delta(*prev, *next, num_prefixes, adv_off, adv_class, policy,
+                                         (flags & OGS_F_WIDE_METRIC) != 0, nh_words, *out,
+                                         workspace, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? OGS_OK : hipFail(e, "route delta");
+}
+
 int ogs_csr_patch(uint64_t* edges, const uint32_t* idx, const uint64_t* val,
                   int32_t n, void* stream) {
   if (n < 0) return fail(OGS_E_INVALID, "n < 0");

@@ -65,6 +65,12 @@ hipError_t launch_route_changes(const uint32_t* changed, int nUnits, int Sp, int
                                 const uint32_t* meta, const uint32_t* metric,
                                 const uint32_t* mask, const ogs_route_changes& out,
                                 hipStream_t stream);
+// route_delta.hip
+hipError_t launch_route_delta(const ogs_spf_out& prev, const ogs_spf_out& next, int P,
+                              const uint32_t* advOff, const uint32_t* advClass,
+                              const ogs_route_delta_policy* policy, bool wide, int W,
+                              const ogs_route_delta_out& out, void* workspace,
+                              hipStream_t stream);
 // csr_patch.hip
 hipError_t launch_csr_patch(uint64_t* edges, const uint32_t* idx, const uint64_t* val,
                             int n, hipStream_t stream);

@@ -103,29 +103,47 @@ struct DiffCtx {
 
 // Best-entry class of a valid route (ogs_route_diff.adv_class): the
 // advertisement's entry as is, or with the hard-drain override.
-__device__ __forceinline__ uint32_t best_class(const DiffCtx& d, uint32_t p, uint32_t meta) {
-  const uint32_t a = d.advOff[p] + (meta >> OGS_ROUTE_BEST_SHIFT);
-  return d.advClass[2u * a + ((meta & OGS_ROUTE_DRAINED) ? 1u : 0u)];
+__device__ __forceinline__ uint32_t best_class(const uint32_t* advOff, const uint32_t* advClass,
+                                               uint32_t p, uint32_t meta) {
+  const uint32_t a = advOff[p] + (meta >> OGS_ROUTE_BEST_SHIFT);
+  return advClass[2u * a + ((meta & OGS_ROUTE_DRAINED) ? 1u : 0u)];
+}
+
+// RibUnicastEntry::operator== (RibEntry.h:81-87) on two records of prefix p
+// (metas am / bm), stated once for the variant diff (route_changed) and the
+// build-to-build delta (route_delta.hip): validity differs, or both are valid
+// and the LOCAL bit, the best entry (by class when advClass is given, else by
+// index + DRAINED), the metric (metricNe()) or a mask word (maskNe(w)) differ.
+// The callers' metric / mask reads stay behind the validity test.
+template <int W, typename MetricNe, typename MaskNe>
+__device__ __forceinline__ bool records_differ(uint32_t am, uint32_t bm, const uint32_t* advOff,
+                                               const uint32_t* advClass, uint32_t p,
+                                               MetricNe metricNe, MaskNe maskNe) {
+  constexpr uint32_t kEq = OGS_ROUTE_DRAINED | OGS_ROUTE_LOCAL |
+      (0xFFFFFFu << OGS_ROUTE_BEST_SHIFT);
+  const bool va = am & OGS_ROUTE_VALID, vb = bm & OGS_ROUTE_VALID;
+  bool ch = va != vb;
+  if (va && vb) {
+    // bestPrefixEntry by value (RibEntry.h:81-87) when classes are given
+    ch = (advClass ? (((am ^ bm) & OGS_ROUTE_LOCAL) != 0u ||
+                      best_class(advOff, advClass, p, am) != best_class(advOff, advClass, p, bm))
+                   : ((am ^ bm) & kEq) != 0u) ||
+        metricNe();
+#pragma unroll
+    for (int w = 0; w < W; ++w) ch |= maskNe(w);
+  }
+  return ch;
 }
 
 template <int W>
 __device__ __forceinline__ bool route_changed(const Rec<W>& r, const DiffCtx& d,
                                               uint32_t Sp, uint32_t p,
                                               uint32_t& upd, uint32_t& del) {
-  constexpr uint32_t kEq = OGS_ROUTE_DRAINED | OGS_ROUTE_LOCAL |
-      (0xFFFFFFu << OGS_ROUTE_BEST_SHIFT);
   const uint32_t bm = d.bMeta[p];
   const bool va = r.meta & OGS_ROUTE_VALID, vb = bm & OGS_ROUTE_VALID;
-  bool ch = va != vb;
-  if (va && vb) {
-    // bestPrefixEntry by value (RibEntry.h:81-87) when classes are given
-    ch = (d.advClass ? (((r.meta ^ bm) & OGS_ROUTE_LOCAL) != 0u ||
-                        best_class(d, p, r.meta) != best_class(d, p, bm))
-                     : ((r.meta ^ bm) & kEq) != 0u) ||
-        r.metric != d.bMetric[p];
-#pragma unroll
-    for (int w = 0; w < W; ++w) ch |= r.mask[w] != d.bMask[size_t(w) * Sp + p];
-  }
+  const bool ch = records_differ<W>(
+      r.meta, bm, d.advOff, d.advClass, p, [&] { return r.metric != d.bMetric[p]; },
+      [&](int w) { return r.mask[w] != d.bMask[size_t(w) * Sp + p]; });
   upd += (va && ch) ? 1u : 0u;
   del += (vb && !va) ? 1u : 0u;
   return ch;

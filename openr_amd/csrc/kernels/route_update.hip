@@ -43,12 +43,7 @@ __global__ __launch_bounds__(kBlock) void route_changes_kernel(
     uint32_t bits = w < words ? row[w] : 0u;
     if (w == words - 1u && (Sp & 31u)) bits &= (1u << (Sp & 31u)) - 1u;
     const uint32_t c = uint32_t(__popc(bits));
-    uint32_t incl = c;  // inclusive wave scan of the popcounts
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t y = __shfl_up(incl, d, 64);
-      if (lane >= uint32_t(d)) incl += y;
-    }
+    const uint32_t incl = wave_inclusive_scan(c, lane);  // of the popcounts
     uint32_t o = pos + incl - c;
     for (; bits; bits &= bits - 1u) {
       const uint32_t p = w * 32u + uint32_t(__builtin_ctz(bits));

@@ -21,6 +21,18 @@ namespace ogs {
 
 constexpr int kBlock = 256;
 
+// Inclusive scan of c across a full wavefront (the changed-record gathers'
+// output positions from their bitmap words' popcounts).
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t c, uint32_t lane) {
+  uint32_t incl = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(incl, d, 64);
+    if (lane >= uint32_t(d)) incl += y;
+  }
+  return incl;
+}
+
 template <typename D>
 struct DistInf {
   static constexpr D value = ~D(0);

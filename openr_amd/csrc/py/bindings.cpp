@@ -1320,6 +1320,16 @@ PYBIND11_MODULE(_decision, m) {
       .def("buildRouteDb",
            [](SpfSolver& s, const std::string& me, const AreaLinkStates& a,
               const PrefixState& ps) { return s.buildRouteDb(me, a, ps); })
+      .def("rebuildRoutes",
+           [](SpfSolver& s, const std::string& me, const AreaLinkStates& a,
+              const PrefixState& ps) -> py::object {
+             auto u = s.rebuildRoutes(me, a, ps);
+             if (!u) return py::none();
+             return fromUpdate(*u);
+           })
+      .def("routeDb", &SpfSolver::routeDb, py::return_value_policy::reference_internal)
+      .def("deltaBuilds", &SpfSolver::deltaBuilds)
+      .def("deltaFallbacks", &SpfSolver::deltaFallbacks)
       .def("createRouteForPrefixOrGetStaticRoute",
            [](SpfSolver& s, const std::string& me, const AreaLinkStates& a,
               const PrefixState& ps, const std::string& prefix) -> py::object {
@@ -1849,6 +1859,123 @@ PYBIND11_MODULE(_decision, m) {
           return std::make_tuple(cold, warm, routes, dCold, dWarm, splitCold, splitWarm);
         },
         py::arg("kind"), py::arg("opts"), py::arg("me"), py::arg("reps"));
+  // Flap rebuild as Decision::rebuildRoutes' full branch sees it
+  // (Decision.cpp:912-927), on twin solvers over twin copies of a generated
+  // LSDB: `flaps` seeded one-link metric flaps (one adjacency of one node's
+  // database moved to another metric; the ingestion is untimed), after each
+  // (a) SpfSolver::rebuildRoutes and (b) buildRouteDb + calculateUpdate +
+  // update, timed in alternating order. The two updates must be equal. One
+  // untimed flap first warms the code objects. Returns the per-flap times
+  // (us), change counts and (a)'s decision.gpu.*_ms splits.
+  m.def("flap_rebuild_bench",
+        [](const std::string& kind, py::dict opts, const std::string& me, int flaps,
+           uint64_t seed) {
+          auto g = genLsdb(kind, opts);
+          std::vector<double> aUs, bUs;
+          std::vector<size_t> changes;
+          std::vector<std::array<double, 4>> splits;
+          uint64_t builds = 0, fallbacks = 0;
+          size_t routes = 0;
+          {
+            py::gil_scoped_release nogil;
+            struct World {
+              AreaLinkStates als;
+              PrefixState ps;
+              SpfSolver solver{"test_node", true, false, false};
+            } A, B;
+            for (World* w : {&A, &B}) {
+              auto& ls = w->als.emplace(g.area, LinkState(g.area, "test_node")).first->second;
+              loadLsdb(g, ls, w->ps);
+            }
+            const char* kSplit[4] = {"decision.gpu.prepare_ms.sum", "decision.gpu.launch_ms.sum",
+                                     "decision.gpu.delta_ms.sum",
+                                     "decision.gpu.materialize_ms.sum"};
+            auto snap = [&]() {
+              std::array<double, 4> a{};
+              const auto c = getDecisionCounters();
+              for (int i = 0; i < 4; ++i) {
+                auto it = c.find(kSplit[i]);
+                a[i] = it == c.end() ? 0.0 : it->second;
+              }
+              return a;
+            };
+            auto usSince = [](std::chrono::steady_clock::time_point t0) {
+              return std::chrono::duration<double, std::micro>(
+                         std::chrono::steady_clock::now() - t0).count();
+            };
+            if (!A.solver.rebuildRoutes(me, A.als, A.ps)) {
+              throw std::runtime_error("no RouteDb for " + me);
+            }
+            DecisionRouteDb heldB = *B.solver.buildRouteDb(me, B.als, B.ps);
+            uint64_t rng = seed;
+            for (int i = 0; i < flaps + 1; ++i) {
+              topogen::AdjDb* d = nullptr;
+              do {
+                d = &g.adjDbs[topogen::splitmix64(rng) % g.adjDbs.size()];
+              } while (d->adjs.empty());
+              topogen::Adj& adj = d->adjs[topogen::splitmix64(rng) % d->adjs.size()];
+              adj.metric = adj.metric > 8 ? adj.metric - int32_t(1 + topogen::splitmix64(rng) % 4)
+                                          : adj.metric + int32_t(1 + topogen::splitmix64(rng) % 4);
+              const AdjacencyDatabase db = toAdjacencyDatabase(*d, g.area);
+              for (World* w : {&A, &B}) w->als.at(g.area).updateAdjacencyDatabase(db, g.area);
+              std::optional<DecisionRouteUpdate> ua;
+              DecisionRouteUpdate ub;
+              double ta = 0, tb = 0;
+              std::array<double, 4> s0{}, s1{};
+              auto runA = [&] {
+                s0 = snap();
+                const auto t0 = std::chrono::steady_clock::now();
+                ua = A.solver.rebuildRoutes(me, A.als, A.ps);
+                ta = usSince(t0);
+                s1 = snap();
+              };
+              auto runB = [&] {
+                const auto t0 = std::chrono::steady_clock::now();
+                auto nb = B.solver.buildRouteDb(me, B.als, B.ps);
+                ub = heldB.calculateUpdate(*nb);
+                heldB.update(ub);
+                tb = usSince(t0);
+              };
+              if (i & 1) {
+                runB();
+                runA();
+              } else {
+                runA();
+                runB();
+              }
+              if (!ua) throw std::runtime_error("no RouteDb for " + me);
+              if (ua->unicastRoutesToUpdate != ub.unicastRoutesToUpdate ||
+                  ua->unicastRoutesToDelete != ub.unicastRoutesToDelete ||
+                  ua->mplsRoutesToUpdate != ub.mplsRoutesToUpdate ||
+                  ua->mplsRoutesToDelete != ub.mplsRoutesToDelete) {
+                throw std::runtime_error("flap " + std::to_string(i) +
+                                         ": rebuildRoutes' update differs from "
+                                         "buildRouteDb + calculateUpdate");
+              }
+              if (i == 0) continue;  // warm-up
+              aUs.push_back(ta);
+              bUs.push_back(tb);
+              changes.push_back(ub.unicastRoutesToUpdate.size() + ub.unicastRoutesToDelete.size());
+              splits.push_back({s1[0] - s0[0], s1[1] - s0[1], s1[2] - s0[2], s1[3] - s0[3]});
+            }
+            if (canonical(A.solver.routeDb()) != canonical(heldB)) {
+              throw std::runtime_error("held RouteDb differs from the full rebuild's");
+            }
+            builds = A.solver.deltaBuilds();
+            fallbacks = A.solver.deltaFallbacks();
+            routes = heldB.unicastRoutes.size();
+          }
+          py::dict out;
+          out["rebuild_us"] = aUs;
+          out["full_us"] = bUs;
+          out["changes"] = changes;
+          out["splits_ms"] = splits;  // prepare, launch, delta, materialize
+          out["delta_builds"] = builds;
+          out["delta_fallbacks"] = fallbacks;
+          out["routes"] = routes;
+          return out;
+        },
+        py::arg("kind"), py::arg("opts"), py::arg("me"), py::arg("flaps"), py::arg("seed"));
   // Host-only f1 materialisation harness (no device): synthetic changed
   // records of `variants` variants x `perVariant` prefixes of a generated
   // topology's source `me` (about 10 % deletions, random next-hop subsets of
