@@ -72,18 +72,28 @@ SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fr
 ASAN_BIN := build/asan/host_asan
 ASAN_REF := build/asan/_refcpu$(EXT)
 ASAN_LOG ?= profiles/r06_asan.log
-$(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp
+ASAN_STUBS := tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp tests/asan/ogs_stub_scenarios.cpp
+$(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp $(ASAN_STUBS)
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
-	  $(HOST) tests/asan/host_asan.cpp tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp \
+	  $(HOST) tests/asan/host_asan.cpp $(ASAN_STUBS) \
+	  -o $@ -lpthread
+# the what-if sweep's scenario expansion and list building, same stubs
+ASAN_SCEN := build/asan/scenario_asan
+$(ASAN_SCEN): $(HOST) $(HOST_H) tests/asan/scenario_asan.cpp $(ASAN_STUBS)
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
+	  $(HOST) tests/asan/scenario_asan.cpp $(ASAN_STUBS) \
 	  -o $@ -lpthread
 $(ASAN_REF): oracle/refcpu/refcpu.cpp oracle/refcpu/refcpu.h oracle/refcpu/bindings.cpp openr_amd/csrc/gen/topogen.h
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -fPIC -shared -I$(PY_INC) -I$(PYBIND_INC) \
 	  oracle/refcpu/refcpu.cpp oracle/refcpu/bindings.cpp -o $@ -lpthread
-asan: $(ASAN_BIN) $(ASAN_REF)
+asan: $(ASAN_BIN) $(ASAN_SCEN) $(ASAN_REF)
 	{ echo "== host_asan (drop-in host code, ASan+UBSan)"; \
 	  ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_BIN) && \
+	  echo "== scenario_asan (what-if scenario expansion, ASan+UBSan)" && \
+	  ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_SCEN) && \
 	  echo "== oracle (refcpu, ASan+UBSan, KATs + generated RouteDbs)" && \
 	  LD_PRELOAD=$$($(CXX) -print-file-name=libasan.so):$$($(CXX) -print-file-name=libubsan.so) \
 	  ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 python3 tools/asan_oracle.py; } 2>&1 | tee $(ASAN_LOG)

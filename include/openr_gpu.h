@@ -54,7 +54,10 @@ extern "C" {
  * ogs_spf_routes_groups / ogs_route_group. 6: execution contexts
  * (ogs_ctx_create / ogs_ctx_set_option / ogs_ctx_* compute calls). 7: knob
  * read-back (ogs_get_option / ogs_ctx_get_option / ogs_option_name).
- * 8: ogs_route_delta. */
+ * 8: ogs_route_delta. Still 8, additive: libraries from the what-if
+ * scenario sweep on also export ogs_spf_routes_scenarios /
+ * ogs_ctx_spf_routes_scenarios; a consumer that may meet an older ABI-8
+ * library detects them by symbol (dlsym). */
 #define OGS_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------ */
@@ -530,6 +533,56 @@ int ogs_spf_routes_variants(const ogs_graph* graph,
                             ogs_route_diff* diff, uint32_t flags,
                             int32_t nh_words, ogs_spf_out* out, void* stream);
 
+/* What-if scenarios of any size: per unit a list of dead directed edges and
+ * a list of hard-drained nodes, both as CSR slices. What a scenario stands
+ * for in the reference:
+ *   links down   the adjacency withdrawn at both ends
+ *                (LinkState::updateAdjacencyDatabase, LinkState.cpp:491-634):
+ *                both directed edges of every failed link (a shared-risk
+ *                group lists all its links);
+ *   node down    LinkState::deleteAdjacencyDatabase (LinkState.cpp:643):
+ *                every edge out of the node and into it. Its prefixes stay
+ *                in the table and lose their routes;
+ *   node drain   the node's database re-sent with isOverloaded
+ *                (updateAdjacencyDatabase, LinkState.cpp:441;
+ *                updateNodeOverloaded, :309): the node stays reachable,
+ *                never transits (LinkState.cpp:741-752) and as an advertiser
+ *                is deprioritised with the drain override.
+ * Entries of dead_edges that are OGS_NODE_NONE or >= the topology's edge
+ * count, and of drain_nodes that are >= its node count, are skipped on the
+ * device. Next-hop link slots stay those of the unmodified CSR row. */
+typedef struct ogs_scenario_mods {
+  const uint32_t* dead_off;    /* [n_units + 1] device, ascending          */
+  const uint32_t* dead_edges;  /* [dead_off[n_units]] topology-local
+                                  DIRECTED edge ids                        */
+  const uint32_t* drain_off;   /* [n_units + 1] or NULL (no drains in this
+                                  call)                                    */
+  const uint32_t* drain_nodes; /* node ids hard-drained in the unit        */
+} ogs_scenario_mods;
+
+/* ogs_spf_routes_variants over scenario lists: diff, the flags
+ * (OGS_F_INCREMENTAL, OGS_F_CHANGED_ONLY), the outputs and
+ * ogs_route_changes_gather keep their meaning, and every rule the two
+ * entries share returns the same status. The dead set is an LDS bitset over
+ * the topology's directed edges, 4 * ceil(max_edges / 32) bytes. With
+ * OGS_F_INCREMENTAL, nh_words 1, max_nodes <= 65535 and the repair's LDS +
+ * the bitset (+ max_nodes with drains) within 160 KB the call runs as the
+ * repair of the base unit's SPF, where a draining unit keeps its own LDS row
+ * of node flags. Otherwise dead lists run the full frontier form (nh_words 1,
+ * 2 or 4), every workgroup building its bitset. Drains are NOT built in that
+ * form -- its chunk records carry a per-topology drained bit -- so a call
+ * with drains that the repair cannot take returns OGS_E_UNSUPPORTED with
+ * nothing launched (as does a bitset past every form's LDS), and the caller
+ * runs each scenario as a topology of its own through ogs_spf_routes. mods,
+ * dead_off or dead_edges NULL, or only one of drain_off / drain_nodes:
+ * OGS_E_INVALID. n_units == 0: OGS_OK. */
+int ogs_spf_routes_scenarios(const ogs_graph* graph,
+                             const ogs_prefix_table* prefixes,
+                             const ogs_unit* units /* device */, int32_t n_units,
+                             const ogs_scenario_mods* mods,
+                             ogs_route_diff* diff, uint32_t flags,
+                             int32_t nh_words, ogs_spf_out* out, void* stream);
+
 /* Compact list of the changed routes of n_units variants (SURVEY.md §8(f)
  * f1): what DecisionRouteDb::calculateUpdate (SpfSolver.cpp:21-56) hands
  * Fib through Decision::rebuildRoutes (Decision.cpp:929-951), gathered from
@@ -730,6 +783,11 @@ int ogs_ctx_spf_routes_variants(ogs_ctx* ctx, const ogs_graph* graph,
                                 int32_t n_units, const ogs_unit_mods* mods,
                                 ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
                                 ogs_spf_out* out, void* stream);
+int ogs_ctx_spf_routes_scenarios(ogs_ctx* ctx, const ogs_graph* graph,
+                                 const ogs_prefix_table* prefixes, const ogs_unit* units,
+                                 int32_t n_units, const ogs_scenario_mods* mods,
+                                 ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
+                                 ogs_spf_out* out, void* stream);
 int ogs_ctx_ksp_paths(ogs_ctx* ctx, const ogs_graph* graph, const ogs_path_unit* units,
                       int32_t n_units, const uint32_t* masks, uint32_t mask_words,
                       uint32_t flags, ogs_path_out* out, void* stream);

@@ -34,6 +34,7 @@ EXPORTS = [
     "ogs_ctx_rib_policy_apply",
     "ogs_get_option", "ogs_ctx_get_option", "ogs_option_name",
     "ogs_route_delta",
+    "ogs_spf_routes_scenarios", "ogs_ctx_spf_routes_scenarios",
 ]
 
 
@@ -79,6 +80,19 @@ class RouteDeltaOut(ctypes.Structure):
                 ("metric", ctypes.c_void_p), ("mask", ctypes.c_void_p),
                 ("sel", ctypes.c_void_p), ("applied", ctypes.c_void_p),
                 ("counter", ctypes.c_void_p), ("header", ctypes.c_void_p)]
+
+
+class ScenarioMods(ctypes.Structure):
+    _fields_ = [("dead_off", ctypes.c_void_p), ("dead_edges", ctypes.c_void_p),
+                ("drain_off", ctypes.c_void_p), ("drain_nodes", ctypes.c_void_p)]
+
+
+class RouteDiff(ctypes.Structure):
+    _fields_ = [("base_meta", ctypes.c_void_p), ("base_metric", ctypes.c_void_p),
+                ("base_mask", ctypes.c_void_p), ("changed", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("base_dist", ctypes.c_void_p),
+                ("base_nh", ctypes.c_void_p), ("adv_class", ctypes.c_void_p),
+                ("base_desc", ctypes.c_void_p), ("base_desc_valid", ctypes.c_int32)]
 
 
 def route_delta_workspace_bytes(num_prefixes):
@@ -136,6 +150,7 @@ def load(path=None):
     plain = {
         "ogs_routes_from_spf": [P, P, P, I32, P, P, P, U32, I32, P, P],
         "ogs_spf_routes_variants": [P, P, P, I32, P, P, U32, I32, P, P],
+        "ogs_spf_routes_scenarios": [P, P, P, I32, P, P, U32, I32, P, P],
         "ogs_ksp_paths": [P, P, I32, P, U32, U32, P, P],
         "ogs_ksp2_paths": [P, P, I32, P, I32, U32, P, P, P],
         "ogs_routes_multiarea": [P, P, P, P, I32, P, P, P, U32, I32, P, P],

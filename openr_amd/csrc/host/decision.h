@@ -1185,9 +1185,12 @@ DecisionRouteDb materializeRouteDb(
 // SURVEY.md §8(f) f1 over config C4: the route updates Decision would hand
 // Fib (Decision::rebuildRoutes incremental branch, Decision.cpp:929-951 =
 // buildRouteDb + DecisionRouteDb::calculateUpdate, SpfSolver.cpp:21-56) for
-// many what-if variants of ONE area, a variant being a set of <= 2 links taken
-// down (adjacency withdrawn at both ends, LinkState.cpp:406-659). All variants
-// run in one launch (ogs_spf_routes_variants, route diff fused in); only the
+// many what-if variants of ONE area, a variant being a set of links taken
+// down (adjacency withdrawn at both ends, LinkState.cpp:406-659) or a
+// Scenario: links down, nodes down, nodes hard-drained. All variants run in
+// one launch (ogs_spf_routes_variants while every variant has at most 8 dead
+// directed edges and no drain, else ogs_spf_routes_scenarios; route diff
+// fused in; form()); only the
 // changed records are gathered on the device (ogs_route_changes_gather) and
 // materialised. Areas with zero / negative link metrics or path sums past 32
 // bits, and sources of degree > 128, run each variant as its own topology
@@ -1206,6 +1209,43 @@ class LinkFailureSweep {
                    const std::vector<std::vector<LinkDown>>& variants,
                    bool enableV4, bool enableBestRouteSelection = false,
                    bool v4OverV6Nexthop = false);
+  // A what-if scenario of any size; what each kind stands for in the reference:
+  //  linksDown     the adjacency removed at both ends (LinkState.cpp:491-634);
+  //                a shared-risk group names all its links
+  //  nodesDown     LinkState::deleteAdjacencyDatabase(node) (LinkState.cpp:643):
+  //                the node's prefixes stay in PrefixState and lose their routes
+  //  nodesDrained  the node's database re-sent with the overload bit
+  //                (LinkState.cpp:441, 309): reachable, never transits (741-752)
+  struct Scenario {
+    std::vector<LinkDown> linksDown;
+    std::vector<std::string> nodesDown, nodesDrained;
+  };
+  // A scenario over the flat topology: dead DIRECTED edge ids (both
+  // directions of every up link named or touching a downed node) and drained
+  // node ids, each sorted and without duplicates; a link already down and a
+  // node already overloaded are left out (no-ops).
+  struct Expanded {
+    std::vector<uint32_t> deadEdges, drainedNodes;
+  };
+  // std::invalid_argument: an unknown node or link, `me` in nodesDown, a node
+  // in both nodesDown and nodesDrained. Host only.
+  static Expanded expandScenario(const LinkState& ls, const std::string& me, const Scenario& sc);
+  LinkFailureSweep(const std::string& myNodeName, const LinkState& ls,
+                   const PrefixState& ps, const std::vector<Scenario>& scenarios,
+                   bool enableV4, bool enableBestRouteSelection = false,
+                   bool v4OverV6Nexthop = false);
+  // How a launch holds "what is removed": kRegisterList every scenario has at
+  // most 8 dead directed edges and no drain (ogs_spf_routes_variants);
+  // kEdgeBitset ogs_spf_routes_scenarios (LDS bitset, drained-flag row);
+  // kTopologyCopies one patched topology per scenario through ogs_spf_routes
+  // (zero / negative / 64-bit metrics, W > 4, and what the scenarios entry
+  // reports unsupported: drains in kFull mode, with W > 1 or past the
+  // repair's LDS budget). Before the first launch: the form the scenarios
+  // alone select. setMode / setListForm select again and drop fetched results.
+  enum Form { kRegisterList = 0, kEdgeBitset = 1, kTopologyCopies = 2 };
+  Form form() const { return form_; }
+  // A/B and tests only: every list through the bitset form
+  void setListForm(bool forceBitset);
   // base RouteDb records (the diff's reference); launch() runs it when needed
   void runBase(void* stream = nullptr);
   // every variant + diff, one launch; records = false keeps only the diff
@@ -1217,7 +1257,10 @@ class LinkFailureSweep {
   // writes only changed records and no per-variant SPF state
   // (OGS_F_CHANGED_ONLY: routeUpdate / counts / changedPrefixes only)
   enum Mode { kFull = 0, kRepair = 1, kChangedOnly = 2 };
-  void setMode(Mode m) { mode_ = m; }
+  void setMode(Mode m) {
+    mode_ = m;
+    reselect();
+  }
   Mode mode() const { return mode_; }
   // counts -> offsets -> device gather of the changed records -> host
   void fetchUpdates(void* stream = nullptr);
@@ -1225,7 +1268,7 @@ class LinkFailureSweep {
   // them (parity tests)
   void fetchRecords(void* stream = nullptr);
 
-  size_t numVariants() const { return dead_.size() / kDeadMax; }
+  size_t numVariants() const { return deadOff_.size() - 1; }
   const DecisionRouteDb& baseRouteDb() const;             // after a launch
   DecisionRouteUpdate routeUpdate(size_t v) const;        // after fetchUpdates
   // every variant's update, materialised on `threads` host threads (0: up to
@@ -1241,10 +1284,16 @@ class LinkFailureSweep {
   uint32_t flags() const;
 
  private:
-  static constexpr int kDeadMax = 4;  // <= 2 links x 2 directions
+  static constexpr uint32_t kRegisterMax = 8;  // ogs_unit_mods.dead_per_unit limit
   static constexpr size_t kDescMaxNodes = 16384;  // ogs_route_diff.base_desc bound
   void exactLaunch(void* stream);
   void exactFetch(void* stream);
+  Form selectForm() const;
+  // a new mode / list form: the form is selected again and what an earlier
+  // launch left fetched (of whatever form) is dropped with it
+  void reselect();
+  void uploadRegisterSlots();
+  bool copies() const { return form_ == kTopologyCopies; }
   const LinkState& ls_;
   const PrefixState& ps_;
   std::string me_, area_;
@@ -1257,9 +1306,16 @@ class LinkFailureSweep {
   bool descValid_{false};  // bDesc_ holds the base's descendant rows
   DeviceBuffer bDesc_;
   Mode mode_{kRepair};
-  std::vector<uint32_t> dead_;
+  // scenario v: dead directed edges deadList_[deadOff_[v] .. deadOff_[v + 1])
+  // and drained nodes drainList_[drainOff_[v] .. drainOff_[v + 1])
+  std::vector<uint32_t> deadOff_{0}, deadList_, drainOff_{0}, drainList_;
+  uint32_t maxDead_{0};  // longest dead list
+  bool forceBitset_{false};
+  Form form_{kRegisterList};
+  int deadPer_{0};  // dDead_'s dead_per_unit (0: not built yet)
   HostBatchImage img_;  // device copy of hb_
   DeviceBuffer dUnits_, dBaseUnit_, dDead_, dAdvClass_;
+  DeviceBuffer dDeadOff_, dDeadList_, dDrainOff_, dDrainList_;
   DeviceBuffer bDist_, bNh_, bMeta_, bMetric_, bMask_, bSel_;
   DeviceBuffer dDist_, dNh_, dMeta_, dMetric_, dMask_, dSel_, dChanged_, dCounts_;
   DeviceBuffer dOffsets_, cPrefix_, cMeta_, cMetric_, cMask_;

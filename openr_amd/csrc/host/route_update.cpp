@@ -4,8 +4,9 @@
 // Reference: Decision::rebuildRoutes (Decision.cpp:912-951) rebuilds the
 // RouteDb after a topology change and publishes
 // DecisionRouteDb::calculateUpdate(old, new) (SpfSolver.cpp:21-56) to Fib.
-// Here the "new" RouteDbs of many link-failure variants come out of one
-// ogs_spf_routes_variants launch with that diff fused in; the changed records
+// Here the "new" RouteDbs of many what-if variants (links down, nodes down,
+// nodes drained) come out of one ogs_spf_routes_variants or
+// ogs_spf_routes_scenarios launch with that diff fused in; the changed records
 // are gathered on the device and only those are materialised into
 // DecisionRouteUpdate (unicastRoutesToUpdate / unicastRoutesToDelete).
 #include <algorithm>
@@ -52,9 +53,113 @@ std::vector<uint32_t> advClasses(const PrefixHostTable& table) {
   return cls;
 }
 
+namespace {
+
+std::vector<LinkFailureSweep::Scenario> linkScenarios(
+    const std::vector<std::vector<LinkFailureSweep::LinkDown>>& variants) {
+  std::vector<LinkFailureSweep::Scenario> out(variants.size());
+  for (size_t v = 0; v < variants.size(); ++v) out[v].linksDown = variants[v];
+  return out;
+}
+
+}  // namespace
+
 LinkFailureSweep::LinkFailureSweep(
     const std::string& myNodeName, const LinkState& ls, const PrefixState& ps,
     const std::vector<std::vector<LinkDown>>& variants, bool enableV4,
+    bool enableBestRouteSelection, bool v4OverV6Nexthop)
+    : LinkFailureSweep(myNodeName, ls, ps, linkScenarios(variants), enableV4,
+                       enableBestRouteSelection, v4OverV6Nexthop) {}
+
+LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
+                                                            const std::string& me,
+                                                            const Scenario& sc) {
+  const FlatTopology& f = ls.flat();
+  auto nodeId = [&](const std::string& node) {
+    auto it = f.id.find(node);
+    if (it == f.id.end()) throw std::invalid_argument("LinkFailureSweep: unknown node " + node);
+    return it->second;
+  };
+  Expanded x;
+  // both directed edges of the link behind edge e of row u, when it is up
+  auto kill = [&](uint32_t u, uint32_t e) {
+    const Link* link = f.edgeLink[e];
+    if (!link->isUp()) return;  // already down: removing it changes nothing
+    x.deadEdges.push_back(e);
+    const uint32_t o = f.id.at(link->getOtherNodeName(f.names[u]));
+    for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
+      if (f.edgeLink[r] == link) x.deadEdges.push_back(r);
+    }
+  };
+  for (const auto& d : sc.linksDown) {
+    const uint32_t u = nodeId(d.node);
+    uint32_t e = f.rowPtr[u];
+    while (e < f.rowPtr[u + 1] && f.edgeLink[e]->getIfaceFromNode(d.node) != d.ifName) ++e;
+    if (e == f.rowPtr[u + 1]) {
+      throw std::invalid_argument("LinkFailureSweep: no link " + d.node + "%" + d.ifName);
+    }
+    kill(u, e);
+  }
+  std::vector<uint32_t> down;
+  for (const auto& n : sc.nodesDown) {
+    if (n == me) throw std::invalid_argument("LinkFailureSweep: " + me + " itself in nodesDown");
+    const uint32_t u = nodeId(n);
+    down.push_back(u);
+    for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) kill(u, e);
+  }
+  for (const auto& n : sc.nodesDrained) {
+    const uint32_t u = nodeId(n);
+    if (std::find(down.begin(), down.end(), u) != down.end()) {
+      throw std::invalid_argument("LinkFailureSweep: " + n + " both down and drained");
+    }
+    if (!(f.nodeFlags[u] & OGS_NODE_OVERLOADED)) x.drainedNodes.push_back(u);
+  }
+  for (auto* l : {&x.deadEdges, &x.drainedNodes}) {  // the same link named twice folds
+    std::sort(l->begin(), l->end());
+    l->erase(std::unique(l->begin(), l->end()), l->end());
+  }
+  return x;
+}
+
+LinkFailureSweep::Form LinkFailureSweep::selectForm() const {
+  if (exact_) return kTopologyCopies;
+  if (maxDead_ <= kRegisterMax && drainList_.empty() && !forceBitset_) return kRegisterList;
+  return kEdgeBitset;  // launch() falls back to copies when the entry refuses
+}
+
+// The lists as ogs_unit_mods slots: 4 a unit (two links, both directions) as
+// every sweep before scenarios had them, up to 8 when a list is longer.
+void LinkFailureSweep::uploadRegisterSlots() {
+  deadPer_ = int(std::max<uint32_t>(4, maxDead_));
+  std::vector<uint32_t> slots(numVariants() * size_t(deadPer_), OGS_NODE_NONE);
+  for (size_t v = 0; v < numVariants(); ++v) {
+    std::copy(deadList_.begin() + deadOff_[v], deadList_.begin() + deadOff_[v + 1],
+              slots.begin() + v * size_t(deadPer_));
+  }
+  dDead_.upload(slots.data(), slots.size());
+}
+
+void LinkFailureSweep::reselect() {
+  form_ = selectForm();
+  recordsRun_ = changedOnlyRun_ = false;
+  offsets_.clear();
+  changed_.clear();
+  counts_.clear();
+  meta_.clear();
+  xDb_.clear();
+  xUpd_.clear();
+  base_.reset();
+  baseMeta_.clear();
+}
+
+void LinkFailureSweep::setListForm(bool forceBitset) {
+  forceBitset_ = forceBitset;
+  reselect();
+}
+
+LinkFailureSweep::LinkFailureSweep(
+    const std::string& myNodeName, const LinkState& ls, const PrefixState& ps,
+    const std::vector<Scenario>& scenarios, bool enableV4,
     bool enableBestRouteSelection, bool v4OverV6Nexthop)
     : ls_(ls),
       ps_(ps),
@@ -82,39 +187,18 @@ LinkFailureSweep::LinkFailureSweep(
   // variants kernel, ogs_spf_routes takes up to 16
   if (W_ > 4) exact_ = true;
 
-  // dead directed edges: both directions of every failed link
-  auto edgeOf = [&](const std::string& node, auto&& pred) -> uint32_t {
-    auto it = f.id.find(node);
-    if (it == f.id.end()) throw std::invalid_argument("LinkFailureSweep: unknown node " + node);
-    for (uint32_t e = f.rowPtr[it->second]; e < f.rowPtr[it->second + 1]; ++e) {
-      if (pred(*f.edgeLink[e])) return e;
-    }
-    return OGS_NODE_NONE;
-  };
-  dead_.assign(variants.size() * kDeadMax, OGS_NODE_NONE);
-  for (size_t v = 0; v < variants.size(); ++v) {
-    if (variants[v].size() * 2 > size_t(kDeadMax)) {
-      throw std::invalid_argument("LinkFailureSweep: more than 2 links in a variant");
-    }
-    size_t k = 0;
-    for (const auto& d : variants[v]) {
-      const Link* link = nullptr;
-      const uint32_t e = edgeOf(d.node, [&](const Link& l) {
-        if (l.getIfaceFromNode(d.node) != d.ifName) return false;
-        link = &l;
-        return true;
-      });
-      if (e == OGS_NODE_NONE) {
-        throw std::invalid_argument("LinkFailureSweep: no link " + d.node + "%" + d.ifName);
-      }
-      const std::string other = link->getOtherNodeName(d.node);
-      const uint32_t r = edgeOf(other, [&](const Link& l) { return &l == link; });
-      dead_[v * kDeadMax + k++] = e;
-      if (r != OGS_NODE_NONE) dead_[v * kDeadMax + k++] = r;
-    }
+  // every scenario's dead directed edges and drained nodes, as CSR lists
+  for (const Scenario& sc : scenarios) {
+    const Expanded x = expandScenario(ls, me_, sc);
+    deadList_.insert(deadList_.end(), x.deadEdges.begin(), x.deadEdges.end());
+    drainList_.insert(drainList_.end(), x.drainedNodes.begin(), x.drainedNodes.end());
+    deadOff_.push_back(uint32_t(deadList_.size()));
+    drainOff_.push_back(uint32_t(drainList_.size()));
+    maxDead_ = std::max(maxDead_, uint32_t(x.deadEdges.size()));
   }
+  form_ = selectForm();
 
-  const size_t U = variants.size(), Sn = size_t(std::max(hb_.maxNodes, 1));
+  const size_t U = scenarios.size(), Sn = size_t(std::max(hb_.maxNodes, 1));
   Sp_ = size_t(std::max(hb_.maxPrefixes, 1));
   words_ = (Sp_ + 31) / 32;
   std::vector<ogs_unit> units(U, ogs_unit{0, s});
@@ -123,7 +207,13 @@ LinkFailureSweep::LinkFailureSweep(
   img_.uploadTable(hb_);
   dUnits_.upload(units.data(), units.size());
   dBaseUnit_.upload(&base, 1);
-  dDead_.upload(dead_.data(), dead_.size());
+  if (form_ == kRegisterList) uploadRegisterSlots();
+  dDeadOff_.upload(deadOff_.data(), deadOff_.size());
+  dDeadList_.upload(deadList_.data(), deadList_.size());
+  if (!drainList_.empty()) {
+    dDrainOff_.upload(drainOff_.data(), drainOff_.size());
+    dDrainList_.upload(drainList_.data(), drainList_.size());
+  }
   {
     const std::vector<uint32_t> cls = advClasses(table_);
     dAdvClass_.upload(cls.data(), cls.size());
@@ -163,12 +253,24 @@ void LinkFailureSweep::exactLaunch(void* stream) {
     const size_t c1 = std::min(T, c0 + kExactChunk), n = c1 - c0;
     HostBatch hb;  // topology t - c0 = the base (t = 0) or variant t - 1
     for (size_t t = c0; t < c1; ++t) {
-      const uint32_t e0 = uint32_t(hb.edges.size());
+      const uint32_t e0 = uint32_t(hb.edges.size()), n0 = uint32_t(hb.nodeFlags.size());
       hb.append(f, ps_, area_);
       if (t == 0) continue;
-      for (int k = 0; k < kDeadMax; ++k) {
-        const uint32_t e = dead_[(t - 1) * kDeadMax + k];
-        if (e != OGS_NODE_NONE) hb.edges[e0 + e] |= OGS_EDGE_DOWN;
+      for (uint32_t i = deadOff_[t - 1]; i < deadOff_[t]; ++i) {
+        hb.edges[e0 + deadList_[i]] |= OGS_EDGE_DOWN;
+      }
+      // a drain, as LinkState::patchFlat encodes it: the node's flag and
+      // OGS_EDGE_DST_OVERLOADED on every edge into it (the reverse of each
+      // edge of its row: links are two-way)
+      for (uint32_t i = drainOff_[t - 1]; i < drainOff_[t]; ++i) {
+        const uint32_t x = drainList_[i];
+        hb.nodeFlags[n0 + x] |= OGS_NODE_OVERLOADED;
+        for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
+          const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
+          for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
+            if (f.edgeLink[r] == f.edgeLink[e]) hb.edges[e0 + r] |= OGS_EDGE_DST_OVERLOADED;
+          }
+        }
       }
     }
     std::vector<ogs_unit> us(n);
@@ -231,7 +333,7 @@ uint32_t LinkFailureSweep::flags() const {
 }
 
 void LinkFailureSweep::runBase(void* stream) {
-  if (exact_) return exactLaunch(stream);
+  if (copies()) return exactLaunch(stream);
   const ogs_graph g = img_.graph(hb_, 1);
   const ogs_prefix_table pt = img_.table(hb_);
   ogs_spf_out out{bDist_.get(), bNh_.as<uint32_t>(), bMeta_.as<uint32_t>(),
@@ -244,7 +346,7 @@ void LinkFailureSweep::runBase(void* stream) {
 }
 
 void LinkFailureSweep::launch(void* stream, bool records) {
-  if (exact_) return exactLaunch(stream);  // records are always written
+  if (copies()) return exactLaunch(stream);  // records are always written
   if (!baseRun_) runBase(stream);
   offsets_.clear();  // results of an earlier launch are stale now
   changed_.clear();
@@ -259,7 +361,6 @@ void LinkFailureSweep::launch(void* stream, bool records) {
                       dMetric_.get(), dMask_.as<uint32_t>(), dSel_.as<uint32_t>()};
     if (changedOnly) out.dist = out.nh = nullptr;  // records of changed routes only
   }
-  ogs_unit_mods mods{dDead_.as<uint32_t>(), kDeadMax};
   // the base's tight-DAG descendant rows: built by the first repair launch
   // after runBase, reused by the next ones (same topology, source, base SPF)
   const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
@@ -272,16 +373,37 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   uint32_t fl = flags();
   if (mode_ != kFull) fl |= OGS_F_INCREMENTAL;
   if (changedOnly) fl |= OGS_F_CHANGED_ONLY;
-  ogsCheck(ogs_spf_routes_variants(&g, &pt, dUnits_.as<ogs_unit>(), int32_t(numVariants()),
-                                   &mods, &diff, fl, W_, &out, stream),
-           "ogs_spf_routes_variants");
+  if (form_ == kRegisterList) {
+    // the lists as ogs_unit_mods slots: 4 a unit (two links, both directions)
+    // as every sweep before scenarios had them, up to 8 when a list is longer
+    if (!deadPer_) uploadRegisterSlots();
+    ogs_unit_mods mods{dDead_.as<uint32_t>(), deadPer_};
+    ogsCheck(ogs_spf_routes_variants(&g, &pt, dUnits_.as<ogs_unit>(), int32_t(numVariants()),
+                                     &mods, &diff, fl, W_, &out, stream),
+             "ogs_spf_routes_variants");
+  } else {
+    const bool drains = !drainList_.empty();
+    ogs_scenario_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
+                           drains ? dDrainOff_.as<uint32_t>() : nullptr,
+                           drains ? dDrainList_.as<uint32_t>() : nullptr};
+    const int rc = ogs_spf_routes_scenarios(&g, &pt, dUnits_.as<ogs_unit>(),
+                                            int32_t(numVariants()), &mods, &diff, fl, W_, &out,
+                                            stream);
+    if (rc == OGS_E_UNSUPPORTED) {
+      // drains the repair cannot take (kFull mode, W > 1, its LDS budget):
+      // one topology per scenario (nothing was launched)
+      form_ = kTopologyCopies;
+      return exactLaunch(stream);
+    }
+    ogsCheck(rc, "ogs_spf_routes_scenarios");
+  }
   descValid_ = diff.base_desc_valid != 0;  // set by the library when it wrote the rows
   recordsRun_ = records;
   changedOnlyRun_ = records && changedOnly;
 }
 
 void LinkFailureSweep::fetchUpdates(void* stream) {
-  if (exact_) return exactFetch(stream);
+  if (copies()) return exactFetch(stream);
   if (!recordsRun_) {
     throw std::logic_error("LinkFailureSweep::fetchUpdates: launch(records=true) first");
   }
@@ -332,7 +454,7 @@ void LinkFailureSweep::fetchUpdates(void* stream) {
 }
 
 void LinkFailureSweep::fetchRecords(void* stream) {
-  if (exact_) return exactFetch(stream);
+  if (copies()) return exactFetch(stream);
   // the diff (bitmap + counts) always; the records when the launch wrote them
   const size_t U = numVariants();
   const size_t R = (recordsRun_ && !changedOnlyRun_) ? U : 0;
@@ -361,7 +483,7 @@ void LinkFailureSweep::fetchRecords(void* stream) {
 }
 
 const DecisionRouteDb& LinkFailureSweep::baseRouteDb() const {
-  if (exact_) {
+  if (copies()) {
     if (!base_) throw std::logic_error("LinkFailureSweep: nothing fetched yet");
     return *base_;
   }
@@ -453,7 +575,7 @@ DecisionRouteUpdate LinkFailureSweep::routeUpdate(size_t v) const {
   if (v >= numVariants() || offsets_.size() != numVariants() + 1) {
     throw std::out_of_range("LinkFailureSweep::routeUpdate: variant / fetchUpdates");
   }
-  if (exact_) return xUpd_.at(v);
+  if (copies()) return xUpd_.at(v);
   const FlatTopology& f = ls_.flat();
   return updateOf(f, f.rowPtr[f.id.at(me_)], me_, table_, changeRecords(), v, v4OverV6_);
 }
@@ -463,12 +585,12 @@ std::vector<DecisionRouteUpdate> LinkFailureSweep::routeUpdates(int threads) con
   if (offsets_.size() != V + 1) {
     throw std::out_of_range("LinkFailureSweep::routeUpdates: fetchUpdates first");
   }
-  if (exact_) return xUpd_;
+  if (copies()) return xUpd_;
   return materializeUpdates(ls_.flat(), me_, table_, changeRecords(), v4OverV6_, threads);
 }
 
 DecisionRouteDb LinkFailureSweep::routeDb(size_t v) const {
-  if (exact_) {
+  if (copies()) {
     if (v >= xDb_.size()) throw std::out_of_range("LinkFailureSweep::routeDb: variant / fetch");
     return xDb_[v];
   }
@@ -489,7 +611,7 @@ DecisionRouteDb LinkFailureSweep::routeDb(size_t v) const {
 std::vector<std::string> LinkFailureSweep::changedPrefixes(size_t v) const {
   if (v >= numVariants()) throw std::out_of_range("LinkFailureSweep: variant");
   std::vector<std::string> out;
-  if (exact_) {
+  if (copies()) {
     if (v >= xUpd_.size()) throw std::logic_error("LinkFailureSweep: nothing fetched yet");
     for (const auto& [p, _] : xUpd_[v].unicastRoutesToUpdate) out.push_back(p);
     out.insert(out.end(), xUpd_[v].unicastRoutesToDelete.begin(),

@@ -48,6 +48,14 @@ hipError_t launch_variants(const ogs_graph& g, const ogs_prefix_table& pt,
                            const ogs_unit_mods* mods, ogs_route_diff* diff,
                            uint32_t flags, int W, const ogs_spf_out& out,
                            hipStream_t stream, int* unsupported);
+// *unsupported: 1 the rule launch_variants shares, 2 drains that the repair
+// cannot take (no OGS_F_INCREMENTAL, W > 1, its LDS budget), 3 a dead bitset
+// past every form's LDS
+hipError_t launch_scenarios(const ogs_graph& g, const ogs_prefix_table& pt,
+                            const ogs_unit* units, int nUnits,
+                            const ogs_scenario_mods& mods, ogs_route_diff* diff,
+                            uint32_t flags, int W, const ogs_spf_out& out,
+                            hipStream_t stream, int* unsupported);
 // route_multiarea.hip
 hipError_t launch_routes_multiarea(const ogs_graph& g, const ogs_prefix_table& pt,
                                    const ogs_area_table& at,
@@ -153,5 +161,18 @@ hipError_t launch_frontier_variants(const ogs_graph& g, const ogs_prefix_table& 
                                     const ogs_unit_mods* mods,
                                     ogs_route_diff* diff, void* scratch,
                                     hipStream_t stream);
+bool scenario_repair_fits(const ogs_graph& g, uint32_t flags, int W,
+                          const ogs_route_diff* diff, bool drains);
+bool scenario_frontier_fits(const ogs_graph& g, uint32_t flags, int W);
+hipError_t launch_scenarios_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                   const uint32_t* key, const ogs_unit* units, int n,
+                                   uint32_t flags, const ogs_spf_out& out,
+                                   const ogs_scenario_mods& mods, ogs_route_diff* diff,
+                                   void* scratch, hipStream_t stream);
+hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
+                                 const uint32_t* key, const ogs_unit* units, int n,
+                                 uint32_t flags, int W, const ogs_spf_out& out,
+                                 const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                                 void* scratch, hipStream_t stream);
 
 }  // namespace ogs

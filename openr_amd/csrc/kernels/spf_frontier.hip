@@ -123,10 +123,20 @@ struct DeadEdges {
   }
 };
 
-template <bool MODS>
+// Dead edges of a what-if scenario (ogs_scenario_mods): a list of any length,
+// kept as an LDS bitset over the topology's directed edges (one word read per
+// test). Built per unit by the workgroup; ids >= E never reach it.
+struct DeadBits {
+  const uint32_t* bits;  // LDS [ceil(E/32)]
+  __device__ __forceinline__ bool has(uint32_t x) const {
+    return (bits[x >> 5] >> (x & 31u)) & 1u;
+  }
+};
+
+template <bool MODS, typename Dead>
 __device__ __forceinline__ void load_chunk(const uint64_t* __restrict__ edges,
                                            uint64_t ch, uint64_t (&x)[kChunk],
-                                           const DeadEdges& dead) {
+                                           const Dead& dead) {
   const uint32_t b = uint32_t(ch >> 32);
   const uint32_t n = ((uint32_t(ch) >> kChunkCntShift) & 15u) + 1u;
 #pragma unroll
@@ -151,10 +161,10 @@ constexpr int kScanBatch = 8;
 // before the current one is relaxed, two chunks of edges in registers (the
 // few-units-per-CU geometries, B >= 512, where a round is a chain of
 // dependent L2 round trips rather than a share of a busy CU).
-template <int B, bool PIPE, bool MODS, typename Act, typename Relax>
+template <int B, bool PIPE, bool MODS, typename Act, typename Relax, typename Dead>
 __device__ __forceinline__ void scan_active(const uint64_t* __restrict__ chunks, uint32_t C,
                                             const uint64_t* __restrict__ edges,
-                                            const DeadEdges& dead, bool slotWalk, Act active,
+                                            const Dead& dead, bool slotWalk, Act active,
                                             Relax relax) {
   const uint32_t tid = threadIdx.x;
   for (uint32_t c0 = tid; c0 < C; c0 += kScanBatch * B) {
@@ -222,12 +232,12 @@ __device__ __forceinline__ void scan_active(const uint64_t* __restrict__ chunks,
 
 // One unit's SPF into LDS (dist[v], nh[v*W + w]); returns after the final
 // workgroup barrier. stamp[] is scratch. B = threads per workgroup.
-template <int W, bool MODS, int B = kBlock>
+template <int W, bool MODS, int B = kBlock, typename Dead = DeadEdges>
 __device__ __forceinline__ void frontier_spf(
     uint32_t N, uint32_t s, const uint64_t* __restrict__ edges,
     const uint64_t* __restrict__ chunks, uint32_t C, bool hop,
     const uint32_t* __restrict__ gRow, uint32_t e0, uint32_t* dist,
-    uint32_t* nh, uint16_t* stamp, uint64_t* tp, const DeadEdges& dead, bool seedRow,
+    uint32_t* nh, uint16_t* stamp, uint64_t* tp, const Dead& dead, bool seedRow,
     bool slotWalk) {
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   const int tid = threadIdx.x;
@@ -382,12 +392,12 @@ __device__ __forceinline__ void frontier_spf(
 // next-hop sets converge in the same rounds (the fabric: 5 rounds instead of
 // 5 + 4 for the two phases above) -- the least fixpoint of spf_core.h, as
 // queue_spf_packed. dn[v] is over dist + nh (8 B per node).
-template <bool MODS, int B = kBlock>
+template <bool MODS, int B = kBlock, typename Dead = DeadEdges>
 __device__ __forceinline__ void frontier_spf_packed(
     uint32_t N, uint32_t s, const uint64_t* __restrict__ edges,
     const uint64_t* __restrict__ chunks, uint32_t C, bool hop,
     const uint32_t* __restrict__ gRow, uint32_t e0, uint64_t* dn, uint8_t* stamp,
-    uint64_t* tp, const DeadEdges& dead, bool seedRow, bool slotWalk, bool preload) {
+    uint64_t* tp, const Dead& dead, bool seedRow, bool slotWalk, bool preload) {
   // u8 round stamps (1 B per node, so 8 C3 units fit a CU): after 256
   // rounds a stale stamp can match again -- a reached node is pushed once
   // more with its current word, a no-op for the monotone fixpoint; an
@@ -525,13 +535,13 @@ __device__ __forceinline__ void for_row(const uint64_t* __restrict__ edges,
   }
 }
 
-template <int W, bool MODS>
+template <int W, bool MODS, typename Dead>
 __device__ __forceinline__ void queue_spf(
     uint32_t N, uint32_t s, const uint64_t* __restrict__ edges,
     const uint32_t* __restrict__ gRow, uint32_t e0,
     const uint8_t* __restrict__ nflags, bool hop, uint32_t* dist, uint32_t* nh,
     uint32_t* stamp, uint16_t* q0, uint16_t* q1, uint32_t* qcnt, uint32_t* ninfo,
-    uint64_t* tp, const DeadEdges& dead) {
+    uint64_t* tp, const Dead& dead) {
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   constexpr uint32_t kDrained = 0x80000000u;
   const int tid = threadIdx.x;
@@ -673,12 +683,12 @@ __device__ __forceinline__ void queue_spf(
 // Rounds of the packed queue SPF from the current list state: round r's
 // list is buffer r & 1 with count slot r % 3 holding n entries (stamps
 // already claim them). Returns the round after the last non-empty one.
-template <bool MODS>
+template <bool MODS, typename Dead = DeadEdges>
 __device__ __forceinline__ uint32_t packed_rounds(
     uint32_t s, const uint64_t* __restrict__ edges, const uint32_t* __restrict__ gRow,
     uint32_t e0, const uint8_t* __restrict__ nflags, bool hop, uint64_t* dn,
     uint32_t* stamp, uint16_t* q0, uint16_t* q1, uint32_t* qcnt, const uint32_t* ninfo,
-    const DeadEdges& dead, uint32_t r, uint32_t n) {
+    const Dead& dead, uint32_t r, uint32_t n) {
   constexpr uint32_t kDrained = 0x80000000u;
   const int tid = threadIdx.x;
   for (; n; ++r) {
@@ -728,13 +738,13 @@ __device__ __forceinline__ uint32_t packed_rounds(
   return r;
 }
 
-template <bool MODS>
+template <bool MODS, typename Dead>
 __device__ __forceinline__ void queue_spf_packed(
     uint32_t N, uint32_t s, const uint64_t* __restrict__ edges,
     const uint32_t* __restrict__ gRow, uint32_t e0,
     const uint8_t* __restrict__ nflags, bool hop, uint64_t* dn, uint32_t* stamp,
     uint16_t* q0, uint16_t* q1, uint32_t* qcnt, uint32_t* ninfo, uint64_t* tp,
-    const DeadEdges& dead) {
+    const Dead& dead) {
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   constexpr uint32_t kDrained = 0x80000000u;
   const int tid = threadIdx.x;
@@ -804,14 +814,20 @@ __device__ uint32_t g_diagStamps[kDiagWgs * 8];
 // only): each runs the unit's SPF and streams one 1/parts prefix range of
 // its RouteDb, part 0 also writes dist / nh. A launch of few units (one
 // rank's shard of the C3 sources) so keeps enough waves streaming per CU.
-template <int W, bool ROUTES, bool MODS, bool DIFF, int QMODE, bool OUTS3, int B = kBlock>
+// Mods = ogs_scenario_mods (MODS): the unit's dead list of any length in an
+// LDS bitset at smem + bitsOff (DeadBits), built by this workgroup -- each of
+// a unit's `parts` workgroups builds its own.
+template <int W, bool ROUTES, bool MODS, bool DIFF, int QMODE, bool OUTS3, int B = kBlock,
+          typename Mods = ogs_unit_mods>
 __device__ __forceinline__ void spf_frontier_body(
     const ogs_graph& g, const ogs_prefix_table& pt, const uint32_t* __restrict__ key,
     const uint64_t* __restrict__ chunks, const uint32_t* __restrict__ nChunk,
     uint32_t cap, const ogs_unit* __restrict__ units, uint32_t flags,
     uint32_t* __restrict__ oDist, uint32_t* __restrict__ oNh, const ogs_spf_out& out,
-    const ogs_unit_mods& mods, const ogs_route_diff& diff, uint32_t parts) {
+    const Mods& mods, const ogs_route_diff& diff, uint32_t parts, uint32_t bitsOff = 0u) {
   constexpr uint32_t kInf = 0xFFFFFFFFu;
+  constexpr bool LIST = std::is_same_v<Mods, ogs_scenario_mods>;
+  static_assert(!LIST || MODS, "a scenario list is a MODS form");
   const int tid = threadIdx.x;
   static_assert(B == kBlock || (OUTS3 && !MODS && !DIFF && (QMODE == 0 || QMODE == 4)),
                 "other block sizes only for the all-sources stream");
@@ -839,12 +855,26 @@ __device__ __forceinline__ void spf_frontier_body(
       : reinterpret_cast<uint32_t*>(q1 + ((Sn + 1u) & ~1u));
   __shared__ uint32_t qcnt[3];
 
-  DeadEdges dead;
+  std::conditional_t<LIST, DeadBits, DeadEdges> dead;
+  if constexpr (!LIST) {
 #pragma unroll
-  for (int k = 0; k < kMaxDead; ++k) {
-    dead.e[k] = (MODS && k < mods.dead_per_unit)
-        ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + k]
-        : OGS_NODE_NONE;
+    for (int k = 0; k < kMaxDead; ++k) {
+      dead.e[k] = (MODS && k < mods.dead_per_unit)
+          ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + k]
+          : OGS_NODE_NONE;
+    }
+  } else {
+    uint32_t* bits = reinterpret_cast<uint32_t*>(smem + bitsOff);  // [list_bits_words(g)]
+    const uint32_t E = gRow[N] - e0;
+    // (one word past E's: load_chunk tests up to kChunk - 1 ids past a row's end)
+    for (uint32_t w = tid; w < (E + 31u) / 32u + 1u; w += B) bits[w] = 0u;
+    __syncthreads();
+    for (uint32_t i = mods.dead_off[u0] + tid; i < mods.dead_off[u0 + 1]; i += B) {
+      const uint32_t e = mods.dead_edges[i];
+      if (e < E) atomicOr(&bits[e >> 5], 1u << (e & 31u));  // else: skipped, never written
+    }
+    __syncthreads();
+    dead.bits = bits;
   }
   uint64_t tp[5] = {0, 0, 0, 0, 0};
 #ifdef OGS_STAMPS
@@ -969,6 +999,25 @@ __global__ __launch_bounds__(B) void spf_frontier_kernel(
                                                              mods, diff, parts);
 }
 
+// ogs_spf_routes_scenarios without the repair: the full recompute over dead
+// lists of any length (LDS bitset at smem + bitsOff, after the unit's SPF state)
+template <int W, bool DIFF, int QMODE>
+__global__ __launch_bounds__(kBlock) void spf_frontier_list_kernel(
+    ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
+    const uint64_t* __restrict__ chunks, const uint32_t* __restrict__ nChunk,
+    uint32_t cap, const ogs_unit* __restrict__ units, uint32_t flags,
+    uint32_t* __restrict__ oDist, uint32_t* __restrict__ oNh, ogs_spf_out out,
+    ogs_scenario_mods mods, ogs_route_diff diff, uint32_t bitsOff) {
+  spf_frontier_body<W, true, true, DIFF, QMODE, false, kBlock>(g, pt, key, chunks, nChunk, cap,
+                                                               units, flags, oDist, oNh, out,
+                                                               mods, diff, 1u, bitsOff);
+}
+
+// words of the list forms' dead bitset (one past the edges': see the body)
+__host__ __device__ inline uint32_t list_bits_words(const ogs_graph& g) {
+  return (uint32_t(g.max_edges) + 31u) / 32u + 1u;
+}
+
 // "spf_seed_row" option: 1 (default) round 1 of the chunk-scan forms relaxes
 // the source's row directly, 0 it scans every chunk record (A/B)
 // EngineOptions::spfSeedRow (engine.h), default 1
@@ -1005,13 +1054,13 @@ int queue_mode(const ogs_graph& g, int W) {
 }
 
 template <int W, bool ROUTES, bool MODS, bool DIFF, int QMODE, bool OUTS3 = false,
-          int B = kBlock>
+          int B = kBlock, typename Mods = ogs_unit_mods>
 hipError_t launch_frontier_q(const ogs_graph& g, const ogs_prefix_table& pt,
                              const uint32_t* key, const uint64_t* chunks,
                              const uint32_t* nChunk, const ogs_unit* units,
                              int nUnits, uint32_t flags, uint32_t* dist,
                              uint32_t* nh, const ogs_spf_out& out,
-                             hipStream_t stream, const ogs_unit_mods& mods,
+                             hipStream_t stream, const Mods& mods,
                              const ogs_route_diff& diff, int parts = 1) {
   const bool scan = QMODE == 0 || QMODE == 4;  // chunk-scan forms: no lists
   const bool ninfo = scan || ninfo_in_lds(uint32_t(g.max_nodes), W);
@@ -1022,10 +1071,17 @@ hipError_t launch_frontier_q(const ogs_graph& g, const ogs_prefix_table& pt,
   if (opts().spfLaneWalk == 0 || (opts().spfLaneWalk < 0 && B < 512)) flags |= kFlagSlotWalk;
   if (!opts().spfPreload) flags |= kFlagNoPreload;
   if (opts().routeStoreNt & 1) flags |= kFlagNtStores;
-  return launch_dyn_lds(spf_frontier_kernel<W, ROUTES, MODS, DIFF, QMODE, OUTS3, B>,
-                        dim3(unsigned(nUnits) * unsigned(parts)), dim3(B), lds, stream, g, pt,
-                        key, chunks, nChunk, chunk_cap(g), units, flags, dist, nh, out, mods,
-                        diff, uint32_t(parts));
+  if constexpr (std::is_same_v<Mods, ogs_scenario_mods>) {
+    static_assert(ROUTES && MODS && !OUTS3 && B == kBlock, "the list form is a variants form");
+    return launch_dyn_lds(spf_frontier_list_kernel<W, DIFF, QMODE>, dim3(unsigned(nUnits)),
+                          dim3(B), lds + 4u * list_bits_words(g), stream, g, pt, key, chunks,
+                          nChunk, chunk_cap(g), units, flags, dist, nh, out, mods, diff, lds);
+  } else {
+    return launch_dyn_lds(spf_frontier_kernel<W, ROUTES, MODS, DIFF, QMODE, OUTS3, B>,
+                          dim3(unsigned(nUnits) * unsigned(parts)), dim3(B), lds, stream, g, pt,
+                          key, chunks, nChunk, chunk_cap(g), units, flags, dist, nh, out, mods,
+                          diff, uint32_t(parts));
+  }
 }
 
 // Geometry of an all-sources RouteDb launch (OUTS3): threads per workgroup
@@ -1096,15 +1152,23 @@ void stream_geometry(int nUnits, int W, int* block, int* parts) {
   *parts = k;
 }
 
-template <int W, bool ROUTES, bool MODS = false, bool DIFF = false>
+template <int W, bool ROUTES, bool MODS = false, bool DIFF = false,
+          typename Mods = ogs_unit_mods>
 hipError_t launch_frontier(const ogs_graph& g, const ogs_prefix_table& pt,
                            const uint32_t* key, const uint64_t* chunks,
                            const uint32_t* nChunk, const ogs_unit* units,
                            int nUnits, uint32_t flags, uint32_t* dist,
                            uint32_t* nh, const ogs_spf_out& out,
-                           hipStream_t stream, const ogs_unit_mods& mods = {},
+                           hipStream_t stream, const Mods& mods = {},
                            const ogs_route_diff& diff = {}) {
-  const int qm = queue_mode(g, W);
+  int qm = queue_mode(g, W);
+  if constexpr (std::is_same_v<Mods, ogs_scenario_mods>) {
+    // the queue forms' lists and the bitset together past the CU's LDS: chunk scan
+    if (frontier_lds_bytes(uint32_t(g.max_nodes), W, true) + 4u * list_bits_words(g) + 64u >
+        160u * 1024u) {
+      qm = 0;
+    }
+  }
   // chunk scan with one-word next-hop sets: the one-phase packed form
   constexpr int kScanMode = W == 1 ? 4 : 0;
   const bool packedScan = W == 1 && opts().spfPackedScan && qm == 0;
@@ -1324,17 +1388,34 @@ size_t desc_scratch_bytes(const ogs_graph& g) {
   return size_t(Sn) * ((Sn + 31u) / 32u) * 4u;
 }
 
+constexpr uint32_t kRepairStaticLds = 32u;  // the kernel's qcnt[3], cnt[2] (+ padding)
 uint32_t repair_lds_bytes(uint32_t Sn) {
   return 8u * Sn + 4u * ((Sn + 3u) & ~3u) + 2u * 2u * ((Sn + 1u) & ~1u) +
       4u * ((Sn + 31u) / 32u) + 16u;
 }
 
-template <bool CHANGED_ONLY>
+// The repair of one unit, for both dead-set forms. LIST = false
+// (ogs_spf_routes_variants): ogs_unit_mods, at most kMaxDead edges in
+// registers (DeadEdges). LIST = true (ogs_spf_routes_scenarios):
+// ogs_scenario_mods, the unit's slice of a CSR list of any length in
+// an LDS bitset (DeadBits) after the A bitset, the seeds from a strided loop
+// over the slice; DRAINS adds, for a unit that hard-drains nodes
+// (LinkState.cpp:309, 441: the overload bit), an LDS byte row of node flags
+// after the bitset -- the topology's with OGS_NODE_OVERLOADED set on the
+// unit's drained nodes -- read by everything below the seeds in place of the
+// topology's row. A drained node x keeps its own distance and next hops and
+// stops relaxing (741-752), so only strict descendants of x in the base tight
+// DAG can move: the seeds are the heads of x's base-tight out-edges. x's own
+// routes change through the flag alone (DRAINED, route selection), so the
+// changed-only route pass also visits prefixes x advertises.
+template <bool CHANGED_ONLY, bool LIST = false, bool DRAINS = false>
 __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
     ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
     const ogs_unit* __restrict__ units, uint32_t flags, uint32_t* __restrict__ oDist,
-    uint32_t* __restrict__ oNh, ogs_spf_out out, ogs_unit_mods mods,
+    uint32_t* __restrict__ oNh, ogs_spf_out out,
+    std::conditional_t<LIST, ogs_scenario_mods, ogs_unit_mods> mods,
     ogs_route_diff diff, const uint32_t* __restrict__ desc) {
+  static_assert(LIST || !DRAINS, "drains come with the list form");
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   const int tid = threadIdx.x;
   const uint32_t u0 = blockIdx.x;
@@ -1345,7 +1426,7 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
   const uint32_t* __restrict__ gRow = g.row_ptr + nb;
   const uint32_t e0 = gRow[0];
   const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* __restrict__ nflags = g.node_flags + nb;
+  const uint8_t* gflags = g.node_flags + nb;  // the base's
   const uint32_t Sn = uint32_t(g.max_nodes);
   const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
   const uint32_t* __restrict__ bD = diff.base_dist;
@@ -1359,40 +1440,98 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
   uint32_t* inA = reinterpret_cast<uint32_t*>(q1 + ((Sn + 1u) & ~1u));   // [Sn/32]
   __shared__ uint32_t qcnt[3], cnt[2];
   auto isA = [&](uint32_t v) { return (inA[v >> 5] >> (v & 31u)) & 1u; };
+  // LIST: the unit's slices, the bitset [ceil(max_edges/32)] and the flag row
+  uint32_t l0 = 0, l1 = 0, r0 = 0, r1 = 0, E = 0;
+  uint32_t* deadBits = nullptr;
+  uint8_t* lflags = nullptr;
+  if constexpr (LIST) {
+    l0 = mods.dead_off[u0];
+    l1 = mods.dead_off[u0 + 1];
+    E = gRow[N] - e0;
+    deadBits = inA + (Sn + 31u) / 32u;
+    if constexpr (DRAINS) {
+      r0 = mods.drain_off[u0];
+      r1 = mods.drain_off[u0 + 1];
+      lflags = reinterpret_cast<uint8_t*>(deadBits + (uint32_t(g.max_edges) + 31u) / 32u);
+    }
+  }
+  const bool drains = DRAINS && r1 > r0;  // unit-uniform
+  // (the drained row is written above the seeds: no restrict on it)
+  typedef const uint8_t* __restrict__ FlagsRestrict;
+  std::conditional_t<DRAINS, const uint8_t*, FlagsRestrict> nflags = drains ? lflags : gflags;
+  // the base's tight DAG (seeds, growth rounds) is told by the base's flags
+  auto relaxesBase = [&](uint32_t v) { return v == s || !(gflags[v] & OGS_NODE_OVERLOADED); };
   auto relaxes = [&](uint32_t v) { return v == s || !(nflags[v] & OGS_NODE_OVERLOADED); };
+  auto seed = [&](uint32_t v) {
+    if (!(atomicOr(&inA[v >> 5], 1u << (v & 31u)) & (1u << (v & 31u)))) {
+      q1[atomicAdd(&qcnt[1], 1u)] = uint16_t(v);
+    }
+  };
+  // head of dead edge e when the edge is tight in the base
+  auto seedOf = [&](uint32_t e) {
+    const uint32_t u = g.edge_src[e0 + e];
+    const uint64_t x = edges[e];
+    const uint32_t lo = static_cast<uint32_t>(x);
+    const uint32_t v = edge_dst(lo);
+    const uint32_t w = hop ? 1u : static_cast<uint32_t>(x >> 32);
+    if (!(lo & OGS_EDGE_DOWN) && relaxesBase(u) && bD[u] != kInf && bD[u] + w == bD[v]) seed(v);
+  };
 
-  DeadEdges dead;
+  std::conditional_t<LIST, DeadBits, DeadEdges> dead;
+  if constexpr (!LIST) {
 #pragma unroll
-  for (int k = 0; k < kMaxDead; ++k) {
-    dead.e[k] = k < mods.dead_per_unit ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + k]
-                                       : OGS_NODE_NONE;
+    for (int k = 0; k < kMaxDead; ++k) {
+      dead.e[k] = k < mods.dead_per_unit ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + k]
+                                         : OGS_NODE_NONE;
+    }
+  } else {
+    dead.bits = deadBits;
+    for (uint32_t w = tid; w < (E + 31u) / 32u; w += kBlock) deadBits[w] = 0u;
+    if (drains) {
+      for (uint32_t v = tid; v < N; v += kBlock) lflags[v] = gflags[v];
+    }
   }
   for (uint32_t w = tid; w < (N + 31u) / 32u; w += kBlock) inA[w] = 0u;
   if (tid < 3) qcnt[tid] = 0u;
   if (tid < 2) cnt[tid] = 0u;
   __syncthreads();
   // ---- seeds: heads of the failed edges that are tight in the base --------
-  // (the seed's edge straight from the list: indexing `dead` by tid would put
-  // the array in scratch memory, and every edge test of the rounds with it)
-  const uint32_t seedEdge = (tid < kMaxDead && tid < mods.dead_per_unit)
-      ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + tid]
-      : OGS_NODE_NONE;
-  if (seedEdge != OGS_NODE_NONE) {
-    const uint32_t e = seedEdge;
-    const uint32_t u = g.edge_src[e0 + e];
-    const uint64_t x = edges[e];
-    const uint32_t lo = static_cast<uint32_t>(x);
-    const uint32_t v = edge_dst(lo);
-    const uint32_t w = hop ? 1u : static_cast<uint32_t>(x >> 32);
-    if (!(lo & OGS_EDGE_DOWN) && relaxes(u) && bD[u] != kInf && bD[u] + w == bD[v]) {
-      if (!(atomicOr(&inA[v >> 5], 1u << (v & 31u)) & (1u << (v & 31u)))) {
-        q1[atomicAdd(&qcnt[1], 1u)] = uint16_t(v);
-      }
+  if constexpr (!LIST) {
+    // (the seed's edge straight from the list: indexing `dead` by tid would put
+    // the array in scratch memory, and every edge test of the rounds with it)
+    const uint32_t seedEdge = (tid < kMaxDead && tid < mods.dead_per_unit)
+        ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + tid]
+        : OGS_NODE_NONE;
+    if (seedEdge != OGS_NODE_NONE) seedOf(seedEdge);
+  } else {
+    for (uint32_t i = l0 + tid; i < l1; i += kBlock) {
+      const uint32_t e = mods.dead_edges[i];
+      if (e >= E) continue;  // OGS_NODE_NONE or a bad id: never outside the bitset
+      atomicOr(&deadBits[e >> 5], 1u << (e & 31u));
+      seedOf(e);
+    }
+    // a drained node's strict descendants: heads of its base-tight out-edges
+    // (not the source, which always relaxes; reached; not drained already)
+    for (uint32_t i = r0 + tid; DRAINS && i < r1; i += kBlock) {
+      const uint32_t x = mods.drain_nodes[i];
+      if (x >= N) continue;
+      const uint8_t fx = gflags[x];
+      lflags[x] = fx | OGS_NODE_OVERLOADED;
+      const uint32_t dx = bD[x];
+      if (x == s || (fx & OGS_NODE_OVERLOADED) || dx == kInf) continue;
+      const uint32_t b = gRow[x] - e0;
+      for_row(edges, b, gRow[x + 1] - e0 - b, [&](uint32_t, uint64_t y) {
+        const uint32_t lo = static_cast<uint32_t>(y);
+        if (lo & OGS_EDGE_DOWN) return;
+        const uint32_t t = edge_dst(lo);
+        if (dx + (hop ? 1u : static_cast<uint32_t>(y >> 32)) == bD[t]) seed(t);
+      });
     }
   }
   __syncthreads();
   uint32_t n = qcnt[1];
-  if (CHANGED_ONLY && n == 0) {  // no failed link on a shortest path: no change
+  // (a unit that drains changes its drained nodes' own routes whatever n)
+  if (CHANGED_ONLY && n == 0 && !drains) {  // no failed link on a shortest path: no change
     if (tid < 2) diff.counts[size_t(u0) * 2 + tid] = 0u;
     if (oDist || oNh) {
       for (uint32_t v = tid; v < N; v += kBlock) {
@@ -1423,7 +1562,7 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
     uint16_t* nxt = (r & 1) ? q0 : q1;
     for (uint32_t i = tid; i < n; i += kBlock) {
       const uint32_t x = cur[i];
-      if (!relaxes(x)) continue;
+      if (!relaxesBase(x)) continue;
       const uint32_t dx = static_cast<uint32_t>(dn[x]);
       const uint32_t b = gRow[x] - e0;
       for_row(edges, b, gRow[x + 1] - e0 - b, [&](uint32_t, uint64_t y) {
@@ -1460,6 +1599,14 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
   __syncthreads();
   packed_rounds<true>(s, edges, gRow, e0, nflags, hop, dn, stamp, q0, q1, qcnt,
                              nullptr, dead, 1u, qcnt[1]);
+  // from here inA only selects the prefixes the changed-only pass visits:
+  // those of the unit's drained nodes join it
+  if constexpr (DRAINS) {
+    for (uint32_t i = r0 + tid; i < r1; i += kBlock) {
+      const uint32_t x = mods.drain_nodes[i];
+      if (x < N) atomicOr(&inA[x >> 5], 1u << (x & 31u));
+    }
+  }
   __syncthreads();
   if (oDist || oNh) {
     for (uint32_t v = tid; v < N; v += kBlock) {
@@ -1527,6 +1674,64 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
   if (tid < 2) diff.counts[size_t(u0) * 2 + tid] = cnt[tid];
 }
 
+// The base's tight-DAG descendant rows for a repair launch (every unit shares
+// topology, source and base SPF: units[0] / diff->base_dist): from the
+// caller's cache when it holds them, else built (into the cache when given,
+// else into `scratch`); NULL when the graph takes the growth rounds.
+uint32_t* repair_desc_rows(const ogs_graph& g, const ogs_unit* units, uint32_t flags,
+                           ogs_route_diff* diff, void* scratch, hipStream_t stream,
+                           hipError_t* err) {
+  *err = hipSuccess;
+  const uint32_t Sn = uint32_t(g.max_nodes);
+  const bool cached = desc_scratch_bytes(g) && diff->base_desc;
+  if (cached && diff->base_desc_valid) return diff->base_desc;
+  if (!desc_scratch_bytes(g) || !(cached || scratch)) return nullptr;
+  const uint32_t words = (Sn + 31u) / 32u;
+  uint32_t* desc = cached ? diff->base_desc : static_cast<uint32_t*>(scratch);
+  const size_t dl = size_t(words) * 4u + 2u * 2u * ((Sn + 1u) & ~1u);
+  hipLaunchKernelGGL(tight_desc_kernel, dim3(Sn), dim3(64), dl, stream, g, units, flags,
+                     diff->base_dist, desc, words);
+  *err = hipGetLastError();
+  if (*err == hipSuccess && cached) diff->base_desc_valid = 1;  // the cache now holds them
+  return desc;
+}
+
+// LDS of the scenario repair: the repair's + the dead bitset (+ the flag row)
+uint32_t scenario_lds_bytes(const ogs_graph& g, bool drains) {
+  return repair_lds_bytes(uint32_t(g.max_nodes)) + 4u * ((uint32_t(g.max_edges) + 31u) / 32u) +
+      (drains ? ((uint32_t(g.max_nodes) + 3u) & ~3u) : 0u);
+}
+
+bool scenario_repair_fits(const ogs_graph& g, uint32_t flags, int W,
+                          const ogs_route_diff* diff, bool drains) {
+  return (flags & OGS_F_INCREMENTAL) && diff && diff->base_dist && diff->base_nh && W == 1 &&
+      g.max_nodes <= 65535 &&
+      scenario_lds_bytes(g, drains) + kRepairStaticLds <= 160u * 1024u;
+}
+
+// ogs_spf_routes_scenarios through the repair; call when scenario_repair_fits().
+hipError_t launch_scenarios_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                   const uint32_t* key, const ogs_unit* units, int n,
+                                   uint32_t flags, const ogs_spf_out& out,
+                                   const ogs_scenario_mods& mods, ogs_route_diff* diff,
+                                   void* scratch, hipStream_t stream) {
+  const bool drains = mods.drain_off != nullptr;
+  const uint32_t lds = scenario_lds_bytes(g, drains);
+  hipError_t e = hipSuccess;
+  hipError_t* err = &e;
+  const bool changedOnly = (flags & OGS_F_CHANGED_ONLY) != 0;
+  auto k = changedOnly ? (drains ? spf_variant_repair_kernel<true, true, true>
+                                 : spf_variant_repair_kernel<true, true, false>)
+                       : (drains ? spf_variant_repair_kernel<false, true, true>
+                                 : spf_variant_repair_kernel<false, true, false>);
+  uint32_t* desc = repair_desc_rows(g, units, flags, diff, scratch, stream, err);
+  if (e != hipSuccess) return e;
+  return launch_dyn_lds(k, dim3(n), dim3(kBlock), lds, stream, g, pt, key, units,
+                        flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
+                        static_cast<uint32_t*>(out.dist), out.nh, out, mods, *diff,
+                        static_cast<const uint32_t*>(desc));
+}
+
 // ogs_spf_routes_variants with OGS_F_INCREMENTAL (W = 1); false when the
 // repair does not apply (the caller then runs the full recompute).
 bool launch_variants_repair(const ogs_graph& g, const ogs_prefix_table& pt,
@@ -1539,7 +1744,7 @@ bool launch_variants_repair(const ogs_graph& g, const ogs_prefix_table& pt,
     return false;
   }
   const uint32_t lds = repair_lds_bytes(uint32_t(g.max_nodes));
-  if (lds > 160u * 1024u) return false;
+  if (lds + kRepairStaticLds > 160u * 1024u) return false;
   const bool changedOnly = (flags & OGS_F_CHANGED_ONLY) != 0;
   auto k = changedOnly ? spf_variant_repair_kernel<true> : spf_variant_repair_kernel<false>;
   if (lds > 64 * 1024) {
@@ -1547,24 +1752,8 @@ bool launch_variants_repair(const ogs_graph& g, const ogs_prefix_table& pt,
                                hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
     if (*err != hipSuccess) return true;
   }
-  // descendant rows of the base tight DAG (every variant shares topology,
-  // source and base SPF: units[0] / diff->base_dist): from the caller's
-  // cache when it holds them, else built (into the cache when given)
-  uint32_t* desc = nullptr;
-  const uint32_t Sn = uint32_t(g.max_nodes);
-  const bool cached = desc_scratch_bytes(g) && diff->base_desc;
-  if (cached && diff->base_desc_valid) {
-    desc = diff->base_desc;
-  } else if (desc_scratch_bytes(g) && (cached || scratch)) {
-    const uint32_t words = (Sn + 31u) / 32u;
-    desc = cached ? diff->base_desc : static_cast<uint32_t*>(scratch);
-    const size_t dl = size_t(words) * 4u + 2u * 2u * ((Sn + 1u) & ~1u);
-    hipLaunchKernelGGL(tight_desc_kernel, dim3(Sn), dim3(64), dl, stream, g, units, flags,
-                       diff->base_dist, desc, words);
-    *err = hipGetLastError();
-    if (*err != hipSuccess) return true;
-    if (cached) diff->base_desc_valid = 1;  // the caller's cache now holds them
-  }
+  uint32_t* desc = repair_desc_rows(g, units, flags, diff, scratch, stream, err);
+  if (*err != hipSuccess) return true;
   hipLaunchKernelGGL(k, dim3(n), dim3(kBlock), lds, stream, g, pt, key, units,
                      flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
                      static_cast<uint32_t*>(out.dist), out.nh, out, *mods, *diff, desc);
@@ -1609,6 +1798,43 @@ hipError_t launch_frontier_variants(const ogs_graph& g, const ogs_prefix_table& 
     case 1: return launch_variants_w<1>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
     case 2: return launch_variants_w<2>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
     case 4: return launch_variants_w<4>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The full recompute over scenario lists (no drains): the fused frontier SPF
+// + RouteDb (+ diff) launch with the dead set in an LDS bitset.
+bool scenario_frontier_fits(const ogs_graph& g, uint32_t flags, int W) {
+  return frontier_fits(g, flags, W) &&
+      frontier_lds_bytes(uint32_t(g.max_nodes), W) + 4u * list_bits_words(g) + 64u <=
+      160u * 1024u;
+}
+
+template <int W>
+hipError_t launch_lists_w(const ogs_graph& g, const ogs_prefix_table& pt, const uint32_t* key,
+                          const uint64_t* chunks, const uint32_t* nChunk,
+                          const ogs_unit* units, int n, uint32_t flags, const ogs_spf_out& out,
+                          const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                          hipStream_t stream) {
+  uint32_t* dist = static_cast<uint32_t*>(out.dist);
+  const ogs_route_diff d = diff ? *diff : ogs_route_diff{};
+  if (diff) return launch_frontier<W, true, true, true>(g, pt, key, chunks, nChunk, units, n, flags, dist, out.nh, out, stream, mods, d);
+  return launch_frontier<W, true, true, false>(g, pt, key, chunks, nChunk, units, n, flags, dist, out.nh, out, stream, mods, d);
+}
+
+hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
+                                 const uint32_t* key, const ogs_unit* units, int n,
+                                 uint32_t flags, int W, const ogs_spf_out& out,
+                                 const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                                 void* scratch, hipStream_t stream) {
+  uint64_t* chunks = nullptr;
+  uint32_t* nChunk = nullptr;
+  hipError_t e = prep_chunks(g, scratch, stream, &chunks, &nChunk);
+  if (e != hipSuccess) return e;
+  switch (W) {
+    case 1: return launch_lists_w<1>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
+    case 2: return launch_lists_w<2>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
+    case 4: return launch_lists_w<4>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
     default: return hipErrorInvalidValue;
   }
 }

@@ -2158,6 +2158,117 @@ PYBIND11_MODULE(_decision, m) {
           return std::make_tuple(launchMs, serveMs, double(routes) / n, names.size());
         });
 
+  // the seeded link-failure variants VariantRunner solves (config C4), as
+  // scenarios' "links" lists: one (node, ifName) end per failed link
+  m.def("link_failure_variants",
+        [](const std::string& kind, py::dict opts, int count, uint64_t seed, int dualPermille) {
+          const auto g = genLsdb(kind, opts);
+          std::vector<std::vector<std::pair<std::string, std::string>>> out;
+          for (const auto& v : topogen::linkFailureVariants(g, count, seed, dualPermille)) {
+            auto& links = out.emplace_back();
+            for (const auto& l : v) links.emplace_back(l.a, l.ifA);
+          }
+          return out;
+        },
+        py::arg("kind"), py::arg("opts"), py::arg("count"), py::arg("seed") = 0xC4F,
+        py::arg("dualPermille") = 500);
+  // What-if sweep over Python-built LinkState / PrefixState objects (kept
+  // alive by the sweep). A scenario is {"links": [(node, ifName), ...],
+  // "nodesDown": [...], "nodesDrained": [...]}, every key optional.
+  auto toScenario = [](const py::dict& d) {
+    LinkFailureSweep::Scenario s;
+    if (d.contains("links")) {
+      for (const auto& l : d["links"].cast<std::vector<std::pair<std::string, std::string>>>()) {
+        s.linksDown.push_back({l.first, l.second});
+      }
+    }
+    if (d.contains("nodesDown")) s.nodesDown = d["nodesDown"].cast<std::vector<std::string>>();
+    if (d.contains("nodesDrained")) {
+      s.nodesDrained = d["nodesDrained"].cast<std::vector<std::string>>();
+    }
+    return s;
+  };
+  m.def("expand_scenario",
+        [toScenario](const LinkState& ls, const std::string& me, const py::dict& sc) {
+          const auto x = LinkFailureSweep::expandScenario(ls, me, toScenario(sc));
+          const FlatTopology& f = ls.flat();
+          std::vector<uint32_t> src(f.edges.size());
+          for (uint32_t u = 0; u + 1 < f.rowPtr.size(); ++u) {
+            for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) src[e] = u;
+          }
+          std::vector<std::tuple<std::string, std::string, std::string>> dead;
+          for (uint32_t e : x.deadEdges) {
+            const std::string& n = f.names[src[e]];
+            dead.emplace_back(n, f.edgeLink[e]->getOtherNodeName(n),
+                              f.edgeLink[e]->getIfaceFromNode(n));
+          }
+          std::sort(dead.begin(), dead.end());
+          std::vector<std::string> drained;
+          for (uint32_t v : x.drainedNodes) drained.push_back(f.names[v]);
+          return py::make_tuple(dead, drained);
+        },
+        py::arg("linkState"), py::arg("me"), py::arg("scenario"));
+  py::class_<LinkFailureSweep>(m, "LinkFailureSweep")
+      .def(py::init([toScenario](const std::string& me, const LinkState& ls,
+                                 const PrefixState& ps, const std::vector<py::dict>& scenarios,
+                                 bool enableV4, bool brs) {
+             std::vector<LinkFailureSweep::Scenario> scs;
+             for (const auto& d : scenarios) scs.push_back(toScenario(d));
+             return std::make_unique<LinkFailureSweep>(me, ls, ps, scs, enableV4, brs);
+           }),
+           py::arg("me"), py::arg("linkState"), py::arg("prefixState"), py::arg("scenarios"),
+           py::arg("enableV4"), py::arg("enableBestRouteSelection") = false,
+           py::keep_alive<1, 3>(), py::keep_alive<1, 4>())
+      .def("setMode", [](LinkFailureSweep& s, int m) {
+             if (m < 0 || m > 2) throw std::invalid_argument("mode must be 0, 1 or 2");
+             s.setMode(LinkFailureSweep::Mode(m));
+           })
+      .def("setListForm", &LinkFailureSweep::setListForm, py::arg("forceBitset"))
+      .def("launch", [](LinkFailureSweep& s, uintptr_t stream, bool records) {
+             py::gil_scoped_release nogil;
+             s.launch(reinterpret_cast<void*>(stream), records);
+           }, py::arg("stream") = 0, py::arg("records") = true)
+      .def("fetchUpdates", [](LinkFailureSweep& s, uintptr_t stream) {
+             s.fetchUpdates(reinterpret_cast<void*>(stream));
+           }, py::arg("stream") = 0)
+      .def("fetchRecords", [](LinkFailureSweep& s, uintptr_t stream) {
+             s.fetchRecords(reinterpret_cast<void*>(stream));
+           }, py::arg("stream") = 0)
+      .def("routeUpdate", [](const LinkFailureSweep& s, size_t v) {
+             return fromUpdate(s.routeUpdate(v));
+           })
+      .def("updatedCanonical", [](const LinkFailureSweep& s, size_t v) {
+             DecisionRouteDb db = s.baseRouteDb();
+             db.update(s.routeUpdate(v));
+             return py::bytes(canonical(db));
+           })
+      .def("routeDbCanonical", [](const LinkFailureSweep& s, size_t v) {
+             return py::bytes(canonical(s.routeDb(v)));
+           })
+      .def("baseCanonical", [](const LinkFailureSweep& s) {
+             return py::bytes(canonical(s.baseRouteDb()));
+           })
+      .def("materializeAll", [](const LinkFailureSweep& s, int threads) {
+             const auto t0 = std::chrono::steady_clock::now();
+             std::vector<DecisionRouteUpdate> ups = s.routeUpdates(threads);
+             const double ms = std::chrono::duration<double, std::milli>(
+                                   std::chrono::steady_clock::now() - t0).count();
+             uint64_t n = 0;
+             for (const auto& u : ups) {
+               n += u.unicastRoutesToUpdate.size() + u.unicastRoutesToDelete.size();
+             }
+             return std::make_pair(n, ms);
+           }, py::arg("threads") = 0, py::call_guard<py::gil_scoped_release>())
+      .def("counts", &LinkFailureSweep::counts)
+      .def("changedPrefixes", &LinkFailureSweep::changedPrefixes)
+      .def("totalChanges", &LinkFailureSweep::totalChanges)
+      .def("numVariants", &LinkFailureSweep::numVariants)
+      .def("nhWords", &LinkFailureSweep::nhWords)
+      .def("form", [](const LinkFailureSweep& s) { return int(s.form()); });
+  m.attr("kRegisterList") = int(LinkFailureSweep::kRegisterList);
+  m.attr("kEdgeBitset") = int(LinkFailureSweep::kEdgeBitset);
+  m.attr("kTopologyCopies") = int(LinkFailureSweep::kTopologyCopies);
+
   py::class_<VariantRunner>(m, "VariantRunner")
       .def(py::init<bool, bool>(), py::arg("enableV4") = true,
            py::arg("enableBestRouteSelection") = false)

@@ -1,0 +1,108 @@
+"""What-if sweep on the C4 WAN (2,000 nodes, one prefix per node) from source
+"0", mode kChangedOnly: one LinkFailureSweep launch per scenario set,
+  (a) every other node down (1,999 scenarios),
+  (b) every other node drained,
+  (c) 2,000 seeded link groups of 16 links,
+  (d) the C4 link-failure variants (bench.py's 10,000, the same generator
+      and seed) through the register form and, in the same process and
+      interleaved, forced through the bitset form.
+Per set: launch + fetchUpdates ms (median of 5 after 2 warm-ups), the
+materialisation of every DecisionRouteUpdate, the total changed routes and the
+form taken. The CPU baseline is the oracle's own loop -- mutate its LinkState,
+buildRouteDb, calculateUpdate, restore -- on one thread over a 64-scenario
+stratified sample of each set, EXTRAPOLATED to the set's size; the sample's
+updates, counts and updated RouteDbs must equal the sweep's.
+
+  python tools/whatif_sweep.py [--nodes 2000] [--sample 64]"""
+import argparse
+import hashlib
+import json
+import os
+import random
+import sys
+import time
+from statistics import median
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+FORMS = {0: "kRegisterList", 1: "kEdgeBitset", 2: "kTopologyCopies"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=0, help="override C4's node count (smoke runs)")
+    ap.add_argument("--sample", type=int, default=64)
+    args = ap.parse_args()
+    import torch  # noqa: F401  (one HIP runtime: torch's)
+    import _refcpu as O
+    import openr_amd
+    import whatif as W
+    from openr_amd.workloads import (C4_DUAL_PERMILLE, C4_OPTS, C4_SEED, C4_SOURCE,
+                                     C4_VARIANTS)
+    openr_amd.require_gpu()
+    M = openr_amd.decision
+    opts = dict(C4_OPTS)
+    if args.nodes:
+        opts["nodes"] = args.nodes
+    me = C4_SOURCE
+    w = W.generated_world(M, "wan", opts)
+    names = sorted(n for n in w.adjdbs if n != me)
+    links = sorted({min((n, a["ifName"]), (a["otherNodeName"], a["otherIfName"]))
+                    for n, d in w.adjdbs.items() for a in d["adjacencies"]})
+    rng = random.Random(0xC4F)
+    sets = [
+        ("a: node down", [{"nodesDown": [n]} for n in names], False),
+        ("b: node drained", [{"nodesDrained": [n]} for n in names], False),
+        ("c: 16-link groups", [{"links": rng.sample(links, 16)} for _ in range(2000)], False),
+        ("d: C4 variants", [{"links": v} for v in M.link_failure_variants(
+            "wan", opts, C4_VARIANTS, C4_SEED, C4_DUAL_PERMILLE)], True),
+    ]
+    print(f"what-if sweep, C4 WAN: {len(w.adjdbs)} nodes, {w.directed_edges()} directed edges, "
+          f"source {me}, mode kChangedOnly")
+    als, ls, ps = w.load(M, me)
+    oracle = W.Oracle(O, w, me)
+    out = []
+    for label, scs, ab in sets:
+        sweeps = []
+        for force in ((False, True) if ab else (False,)):
+            sw = M.LinkFailureSweep(me, ls, ps, scs, True, False)
+            sw.setMode(2)
+            sw.setListForm(force)
+            sweeps.append(sw)
+        # interleaved: one timed series per sweep, alternating
+        ms = [[] for _ in sweeps]
+        for i in range(7):
+            for k, sw in enumerate(sweeps):
+                t0 = time.perf_counter()
+                sw.launch()
+                sw.fetchUpdates()
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        idx = sorted({i * len(scs) // args.sample for i in range(args.sample)})
+        t0 = time.perf_counter()
+        for i in idx:  # the timed loop: mutate, buildRouteDb, calculateUpdate, restore
+            oracle.answer(scs[i], canonical=False)
+        cpu_ms = (time.perf_counter() - t0) * 1e3 / len(idx)
+        answers = [oracle.answer(scs[i]) for i in idx]
+        digest = hashlib.sha1()
+        for _, canon in answers:
+            digest.update(canon)
+        for k, sw in enumerate(sweeps):
+            W.check_sweep(sw, answers, label, idx)  # raises on any difference
+            n, mat_ms = sw.materializeAll(0)
+            row = dict(set=label, scenarios=len(scs), form=FORMS[sw.form()],
+                       sweep_ms=median(ms[k][2:]), materialize_ms=mat_ms, changed_routes=n,
+                       cpu_ms_per_scenario=cpu_ms, cpu_ms_extrapolated=cpu_ms * len(scs),
+                       sample=len(idx), sample_digest=digest.hexdigest()[:16])
+            out.append(row)
+            print(f"  {label:18s} {len(scs):6d} scenarios  {row['form']:15s} "
+                  f"launch+fetch {row['sweep_ms']:8.3f} ms  materialise {mat_ms:8.3f} ms  "
+                  f"changed routes {n:9d}  | oracle loop {cpu_ms:7.3f} ms/scenario x "
+                  f"{len(scs)} = {cpu_ms * len(scs) / 1e3:8.2f} s (extrapolated from "
+                  f"{len(idx)}); sample equal, sha1 {row['sample_digest']}")
+    print(json.dumps(dict(workload="c4_whatif_sweep", nodes=len(w.adjdbs), rows=out)))
+
+
+if __name__ == "__main__":
+    main()
