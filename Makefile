@@ -72,7 +72,8 @@ SAN := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-fr
 ASAN_BIN := build/asan/host_asan
 ASAN_REF := build/asan/_refcpu$(EXT)
 ASAN_LOG ?= profiles/r06_asan.log
-ASAN_STUBS := tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp tests/asan/ogs_stub_scenarios.cpp
+ASAN_STUBS := tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp tests/asan/ogs_stub_scenarios.cpp \
+  tests/asan/ogs_stub_whatif.cpp
 $(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp $(ASAN_STUBS)
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
@@ -85,6 +86,16 @@ $(ASAN_SCEN): $(HOST) $(HOST_H) tests/asan/scenario_asan.cpp $(ASAN_STUBS)
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
 	  $(HOST) tests/asan/scenario_asan.cpp $(ASAN_STUBS) \
 	  -o $@ -lpthread
+# the what-if sweep's metric-override and soft-drain expansion, same stubs;
+# `make asan-whatif` builds and runs this program alone
+ASAN_WHATIF := build/asan/whatif_asan
+$(ASAN_WHATIF): $(HOST) $(HOST_H) tests/asan/whatif_asan.cpp $(ASAN_STUBS)
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
+	  $(HOST) tests/asan/whatif_asan.cpp $(ASAN_STUBS) \
+	  -o $@ -lpthread
+asan-whatif: $(ASAN_WHATIF)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_WHATIF)
 $(ASAN_REF): oracle/refcpu/refcpu.cpp oracle/refcpu/refcpu.h oracle/refcpu/bindings.cpp openr_amd/csrc/gen/topogen.h
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -fPIC -shared -I$(PY_INC) -I$(PYBIND_INC) \
@@ -102,4 +113,4 @@ clean:
 	rm -f $(LIB) $(MOD) $(STAMPS) $(CCONS) $(KOBJ) $(SOBJ)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean stamps asan
+.PHONY: all oracle clean stamps asan asan-whatif

@@ -56,8 +56,9 @@ extern "C" {
  * read-back (ogs_get_option / ogs_ctx_get_option / ogs_option_name).
  * 8: ogs_route_delta. Still 8, additive: libraries from the what-if
  * scenario sweep on also export ogs_spf_routes_scenarios /
- * ogs_ctx_spf_routes_scenarios; a consumer that may meet an older ABI-8
- * library detects them by symbol (dlsym). */
+ * ogs_ctx_spf_routes_scenarios, and from the metric / soft-drain sweep on
+ * ogs_spf_routes_whatif / ogs_ctx_spf_routes_whatif; a consumer that may
+ * meet an older ABI-8 library detects them by symbol (dlsym). */
 #define OGS_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------ */
@@ -583,6 +584,76 @@ int ogs_spf_routes_scenarios(const ogs_graph* graph,
                              ogs_route_diff* diff, uint32_t flags,
                              int32_t nh_words, ogs_spf_out* out, void* stream);
 
+/* What-if scenarios that also MOVE things: per unit, besides the dead list,
+ * node flag bits and link metric overrides. What the two new kinds stand for
+ * in the reference:
+ *   link cost-out    an adjacency re-sent with another metric (setLinkMetric /
+ *                    setAdjacencyMetric, LinkMonitor.cpp:1003-1006). A link's
+ *                    SPF weight is the max of its two directions
+ *                    (LinkState.h:171-174): the caller lists BOTH directed
+ *                    edges of the link with that max;
+ *   node soft-drain  the node's database re-sent with nodeMetricIncrementVal
+ *                    (LinkMonitor.cpp:971-1001): metric overrides on every up
+ *                    link of the node and OGS_NODE_SOFTDRAIN |
+ *                    OGS_NODE_METRICINC in its flags, which route selection
+ *                    reads (SpfSolver.cpp:511-551).
+ * node_bits are ORed into the node's flags for that unit: OGS_NODE_OVERLOADED
+ * is exactly ogs_scenario_mods' drain. A node appears at most once per unit.
+ * Each unit's metric slice lists directed edge ids ASCENDING WITHOUT
+ * DUPLICATES; metric_vals are the new 32-bit weights, 1 .. 2^31 - 1.
+ * Rules:
+ *   - ids >= the topology's edge / node count are skipped before they index
+ *     anything;
+ *   - an edge in both the dead and the metric list is dead;
+ *   - under OGS_F_HOP_METRIC the metric lists are ignored;
+ *   - an unsorted slice may pick either value of the slice for an edge but
+ *     never reads out of bounds;
+ *   - a unit whose metric slice holds a value of 0 or >= 2^31 (for an edge id
+ *     in range) is REFUSED on the device: its counts are {OGS_WHATIF_REFUSED,
+ *     OGS_WHATIF_REFUSED}, its `changed` row stays zero and it writes no
+ *     record; the other units are unaffected. Such weights belong to the
+ *     exact domain (ogs_spf_routes with OGS_F_WIDE_METRIC over a patched
+ *     topology). */
+#define OGS_WHATIF_REFUSED 0xFFFFFFFFu
+typedef struct ogs_whatif_mods {
+  const uint32_t* dead_off;     /* [n_units + 1] device, ascending          */
+  const uint32_t* dead_edges;   /* as ogs_scenario_mods                     */
+  const uint32_t* node_off;     /* [n_units + 1] or NULL (no node bits in
+                                   this call); with node_ids and node_bits  */
+  const uint32_t* node_ids;     /* node ids whose flags change in the unit  */
+  const uint8_t* node_bits;     /* OGS_NODE_* bits ORed into each           */
+  const uint32_t* metric_off;   /* [n_units + 1] or NULL (no overrides in
+                                   this call); with metric_edges / _vals    */
+  const uint32_t* metric_edges; /* directed edge ids, ascending per unit    */
+  const uint32_t* metric_vals;  /* the new weight of each                   */
+  uint32_t max_metric_per_unit; /* >= the longest metric slice (LDS sizing) */
+} ogs_whatif_mods;
+
+/* ogs_spf_routes_scenarios with node bits and metric overrides: the same
+ * arguments, flags, outputs, diff and ogs_route_changes_gather contract, and
+ * every rule the entries share returns the same status. With
+ * OGS_F_INCREMENTAL, nh_words 1, max_nodes <= 65535 and the LDS budget below
+ * the call runs as the repair of the base unit's SPF: a raised metric only
+ * lengthens paths, so the heads of raised base-tight edges seed the repair
+ * like dead ones; a unit that LOWERS a metric recomputes from the source
+ * inside the same kernel and compares every prefix. Otherwise metric and dead
+ * lists run the full frontier form (nh_words 1, 2 or 4), where a lowered
+ * metric is ordinary. Node bits are not built in that form.
+ * LDS of the repair: the scenarios entry's + 4 * ceil(max_edges / 32) (the
+ * "overridden" bitset) + 8 * max_metric_per_unit (+ max_nodes with node bits),
+ * within 160 KB. OGS_E_UNSUPPORTED with nothing launched: where the scenarios
+ * entry returns it, when node bits are present and the repair cannot take the
+ * call, and when the bitsets and the slice fit no form's LDS. mods, dead_off
+ * or dead_edges NULL, or an incomplete node or metric triple: OGS_E_INVALID.
+ * n_units == 0: OGS_OK. A unit whose metric slice is longer than
+ * max_metric_per_unit is refused like one with a bad value. */
+int ogs_spf_routes_whatif(const ogs_graph* graph,
+                          const ogs_prefix_table* prefixes,
+                          const ogs_unit* units /* device */, int32_t n_units,
+                          const ogs_whatif_mods* mods,
+                          ogs_route_diff* diff, uint32_t flags,
+                          int32_t nh_words, ogs_spf_out* out, void* stream);
+
 /* Compact list of the changed routes of n_units variants (SURVEY.md §8(f)
  * f1): what DecisionRouteDb::calculateUpdate (SpfSolver.cpp:21-56) hands
  * Fib through Decision::rebuildRoutes (Decision.cpp:929-951), gathered from
@@ -788,6 +859,11 @@ int ogs_ctx_spf_routes_scenarios(ogs_ctx* ctx, const ogs_graph* graph,
                                  int32_t n_units, const ogs_scenario_mods* mods,
                                  ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
                                  ogs_spf_out* out, void* stream);
+int ogs_ctx_spf_routes_whatif(ogs_ctx* ctx, const ogs_graph* graph,
+                              const ogs_prefix_table* prefixes, const ogs_unit* units,
+                              int32_t n_units, const ogs_whatif_mods* mods,
+                              ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
+                              ogs_spf_out* out, void* stream);
 int ogs_ctx_ksp_paths(ogs_ctx* ctx, const ogs_graph* graph, const ogs_path_unit* units,
                       int32_t n_units, const uint32_t* masks, uint32_t mask_words,
                       uint32_t flags, ogs_path_out* out, void* stream);

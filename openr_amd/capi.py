@@ -35,7 +35,20 @@ EXPORTS = [
     "ogs_get_option", "ogs_ctx_get_option", "ogs_option_name",
     "ogs_route_delta",
     "ogs_spf_routes_scenarios", "ogs_ctx_spf_routes_scenarios",
+    "ogs_spf_routes_whatif", "ogs_ctx_spf_routes_whatif",
 ]
+
+OGS_WHATIF_REFUSED = 0xFFFFFFFF
+
+
+class WhatifMods(ctypes.Structure):
+    """ogs_whatif_mods: per unit, dead edges, node flag bits and metric
+    overrides (device pointers; NULL node / metric triples: none)."""
+    _fields_ = [("dead_off", ctypes.c_void_p), ("dead_edges", ctypes.c_void_p),
+                ("node_off", ctypes.c_void_p), ("node_ids", ctypes.c_void_p),
+                ("node_bits", ctypes.c_void_p),
+                ("metric_off", ctypes.c_void_p), ("metric_edges", ctypes.c_void_p),
+                ("metric_vals", ctypes.c_void_p), ("max_metric_per_unit", ctypes.c_uint32)]
 
 
 class Graph(ctypes.Structure):
@@ -151,6 +164,7 @@ def load(path=None):
         "ogs_routes_from_spf": [P, P, P, I32, P, P, P, U32, I32, P, P],
         "ogs_spf_routes_variants": [P, P, P, I32, P, P, U32, I32, P, P],
         "ogs_spf_routes_scenarios": [P, P, P, I32, P, P, U32, I32, P, P],
+        "ogs_spf_routes_whatif": [P, P, P, I32, P, P, U32, I32, P, P],
         "ogs_ksp_paths": [P, P, I32, P, U32, U32, P, P],
         "ogs_ksp2_paths": [P, P, I32, P, I32, U32, P, P, P],
         "ogs_routes_multiarea": [P, P, P, P, I32, P, P, P, U32, I32, P, P],

@@ -1187,10 +1187,12 @@ DecisionRouteDb materializeRouteDb(
 // buildRouteDb + DecisionRouteDb::calculateUpdate, SpfSolver.cpp:21-56) for
 // many what-if variants of ONE area, a variant being a set of links taken
 // down (adjacency withdrawn at both ends, LinkState.cpp:406-659) or a
-// Scenario: links down, nodes down, nodes hard-drained. All variants run in
-// one launch (ogs_spf_routes_variants while every variant has at most 8 dead
-// directed edges and no drain, else ogs_spf_routes_scenarios; route diff
-// fused in; form()); only the
+// Scenario: links down, nodes down, nodes hard-drained, link metrics
+// overridden, nodes soft-drained. All variants run in one launch
+// (ogs_spf_routes_variants while every variant has at most 8 dead directed
+// edges and no drain, else ogs_spf_routes_scenarios, or ogs_spf_routes_whatif
+// when a scenario moves a metric or soft-drains a node; route diff fused in;
+// form()); only the
 // changed records are gathered on the device (ogs_route_changes_gather) and
 // materialised. Areas with zero / negative link metrics or path sums past 32
 // bits, and sources of degree > 128, run each variant as its own topology
@@ -1216,19 +1218,53 @@ class LinkFailureSweep {
   //                the node's prefixes stay in PrefixState and lose their routes
   //  nodesDrained  the node's database re-sent with the overload bit
   //                (LinkState.cpp:441, 309): reachable, never transits (741-752)
+  //  linkMetrics   one adjacency re-sent with another metric (setLinkMetric /
+  //                setAdjacencyMetric, LinkMonitor.cpp:1003-1006): one direction,
+  //                as the reference publishes it; the link's SPF weight is the
+  //                max of its two directions (LinkState.h:171-174). A lower
+  //                metric is allowed
+  //  nodesSoftDrained  the node's database re-sent with nodeMetricIncrementVal
+  //                = increment >= 1 (LinkMonitor.cpp:971-1001): every adjacency
+  //                metric moves to published - current increment + increment
+  //                (after the scenario's own linkMetrics), and route selection
+  //                reads the value (SpfSolver.cpp:511-551). The source may be
+  //                soft-drained
+  struct LinkMetric {  // (node, its interface) and the metric it now sends
+    std::string node, ifName;
+    int64_t metric{1};
+  };
+  struct SoftDrain {
+    std::string node;
+    int64_t increment{1};
+  };
   struct Scenario {
     std::vector<LinkDown> linksDown;
     std::vector<std::string> nodesDown, nodesDrained;
+    std::vector<LinkMetric> linkMetrics;
+    std::vector<SoftDrain> nodesSoftDrained;
   };
   // A scenario over the flat topology: dead DIRECTED edge ids (both
   // directions of every up link named or touching a downed node) and drained
   // node ids, each sorted and without duplicates; a link already down and a
   // node already overloaded are left out (no-ops).
+  // metricEdges / metricVals: the directed edges whose weight moves (both of
+  // a link, the max of its directions), ascending, and the new weight as
+  // Link::getMaxMetric would give it (a negative i32 metric reads >= 2^32);
+  // a link the scenario takes down or that is down already, and a link whose
+  // weight stays, are left out. flagNodes / flagBits: nodes, ascending, and
+  // the OGS_NODE_* bits the scenario adds to each (hard drain:
+  // OGS_NODE_OVERLOADED, soft drain: OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC),
+  // bits the node carries already left out.
   struct Expanded {
     std::vector<uint32_t> deadEdges, drainedNodes;
+    std::vector<uint32_t> metricEdges;
+    std::vector<uint64_t> metricVals;
+    std::vector<uint32_t> flagNodes;
+    std::vector<uint8_t> flagBits;
   };
   // std::invalid_argument: an unknown node or link, `me` in nodesDown, a node
-  // in both nodesDown and nodesDrained. Host only.
+  // in both nodesDown and nodesDrained or nodesSoftDrained, an increment < 1.
+  // Host only.
   static Expanded expandScenario(const LinkState& ls, const std::string& me, const Scenario& sc);
   LinkFailureSweep(const std::string& myNodeName, const LinkState& ls,
                    const PrefixState& ps, const std::vector<Scenario>& scenarios,
@@ -1236,12 +1272,15 @@ class LinkFailureSweep {
                    bool v4OverV6Nexthop = false);
   // How a launch holds "what is removed": kRegisterList every scenario has at
   // most 8 dead directed edges and no drain (ogs_spf_routes_variants);
-  // kEdgeBitset ogs_spf_routes_scenarios (LDS bitset, drained-flag row);
+  // kEdgeBitset ogs_spf_routes_scenarios (LDS bitset, drained-flag row), or
+  // ogs_spf_routes_whatif when a scenario carries a metric or a soft drain;
   // kTopologyCopies one patched topology per scenario through ogs_spf_routes
   // (zero / negative / 64-bit metrics, W > 4, and what the scenarios entry
-  // reports unsupported: drains in kFull mode, with W > 1 or past the
-  // repair's LDS budget). Before the first launch: the form the scenarios
-  // alone select. setMode / setListForm select again and drop fetched results.
+  // or what-if entry reports unsupported: drains / soft drains in kFull mode,
+  // with W > 1 or past the repair's LDS budget; also an overridden weight of
+  // 0, a negative one, or one past the 32-bit path-sum guard). Before the
+  // first launch: the form the scenarios alone select. setMode / setListForm
+  // select again and drop fetched results.
   enum Form { kRegisterList = 0, kEdgeBitset = 1, kTopologyCopies = 2 };
   Form form() const { return form_; }
   // A/B and tests only: every list through the bitset form
@@ -1310,6 +1349,15 @@ class LinkFailureSweep {
   // and drained nodes drainList_[drainOff_[v] .. drainOff_[v + 1])
   std::vector<uint32_t> deadOff_{0}, deadList_, drainOff_{0}, drainList_;
   uint32_t maxDead_{0};  // longest dead list
+  // metric overrides metricEdge_ / metricVal_[metricOff_[v] .. metricOff_[v + 1])
+  // and flag bits flagNode_ / flagBits_[flagOff_[v] .. flagOff_[v + 1]) (the
+  // hard drains of drainList_ among them); whatif_: some scenario has either
+  std::vector<uint32_t> metricOff_{0}, metricEdge_, flagOff_{0}, flagNode_;
+  std::vector<uint64_t> metricVal_;
+  std::vector<uint8_t> flagBits_;
+  uint32_t maxMetricList_{0};
+  bool whatif_{false};
+  DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_, dFlagOff_, dFlagNode_, dFlagBits_;
   bool forceBitset_{false};
   Form form_{kRegisterList};
   int deadPer_{0};  // dDead_'s dead_per_unit (0: not built yet)

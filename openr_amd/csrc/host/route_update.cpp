@@ -12,7 +12,9 @@
 #include <algorithm>
 #include <atomic>
 #include <exception>
+#include <map>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <thread>
 
@@ -81,10 +83,21 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
     return it->second;
   };
   Expanded x;
+  std::set<const Link*> killed;
+  // edge of row u behind interface ifName
+  auto edgeOf = [&](uint32_t u, const std::string& node, const std::string& ifName) {
+    uint32_t e = f.rowPtr[u];
+    while (e < f.rowPtr[u + 1] && f.edgeLink[e]->getIfaceFromNode(node) != ifName) ++e;
+    if (e == f.rowPtr[u + 1]) {
+      throw std::invalid_argument("LinkFailureSweep: no link " + node + "%" + ifName);
+    }
+    return e;
+  };
   // both directed edges of the link behind edge e of row u, when it is up
   auto kill = [&](uint32_t u, uint32_t e) {
     const Link* link = f.edgeLink[e];
     if (!link->isUp()) return;  // already down: removing it changes nothing
+    killed.insert(link);
     x.deadEdges.push_back(e);
     const uint32_t o = f.id.at(link->getOtherNodeName(f.names[u]));
     for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
@@ -93,12 +106,7 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
   };
   for (const auto& d : sc.linksDown) {
     const uint32_t u = nodeId(d.node);
-    uint32_t e = f.rowPtr[u];
-    while (e < f.rowPtr[u + 1] && f.edgeLink[e]->getIfaceFromNode(d.node) != d.ifName) ++e;
-    if (e == f.rowPtr[u + 1]) {
-      throw std::invalid_argument("LinkFailureSweep: no link " + d.node + "%" + d.ifName);
-    }
-    kill(u, e);
+    kill(u, edgeOf(u, d.node, d.ifName));
   }
   std::vector<uint32_t> down;
   for (const auto& n : sc.nodesDown) {
@@ -118,12 +126,90 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
     std::sort(l->begin(), l->end());
     l->erase(std::unique(l->begin(), l->end()), l->end());
   }
+  // ---- metrics: what every touched link's two directions would carry ------
+  // (keyed by the edge of the link in its first node's row: a stable order)
+  struct Moved {
+    const Link* link;
+    LinkStateMetric m[2];  // from firstNodeName(), from secondNodeName()
+  };
+  std::map<const Link*, Moved> moved;
+  auto sideMetric = [&](const Link* l, const std::string& node) -> LinkStateMetric& {
+    auto it = moved.find(l);
+    if (it == moved.end()) {
+      it = moved.emplace(l, Moved{l, {l->getMetricFromNode(l->firstNodeName()),
+                                      l->getMetricFromNode(l->secondNodeName())}}).first;
+    }
+    return it->second.m[node == l->firstNodeName() ? 0 : 1];
+  };
+  auto i32 = [](int64_t v, const char* what) {
+    if (v < INT32_MIN || v > INT32_MAX) {
+      throw std::invalid_argument(std::string("LinkFailureSweep: ") + what + " outside i32");
+    }
+    return static_cast<LinkStateMetric>(static_cast<int64_t>(static_cast<int32_t>(v)));
+  };
+  for (const auto& d : sc.linkMetrics) {
+    const uint32_t u = nodeId(d.node);
+    const Link* l = f.edgeLink[edgeOf(u, d.node, d.ifName)];
+    sideMetric(l, d.node) = i32(d.metric, "link metric");
+  }
+  std::map<uint32_t, uint8_t> bits;
+  for (uint32_t u : x.drainedNodes) bits[u] |= uint8_t(OGS_NODE_OVERLOADED);
+  std::map<uint32_t, int64_t> soft;
+  for (const auto& d : sc.nodesSoftDrained) {
+    const uint32_t u = nodeId(d.node);
+    if (std::find(down.begin(), down.end(), u) != down.end()) {
+      throw std::invalid_argument("LinkFailureSweep: " + d.node + " both down and soft-drained");
+    }
+    if (d.increment < 1) {
+      throw std::invalid_argument("LinkFailureSweep: soft-drain increment of " + d.node + " < 1");
+    }
+    i32(d.increment, "soft-drain increment");
+    auto [it, fresh] = soft.emplace(u, d.increment);
+    if (!fresh && it->second != d.increment) {
+      throw std::invalid_argument("LinkFailureSweep: " + d.node + " soft-drained twice");
+    }
+  }
+  for (const auto& [u, inc] : soft) {
+    const std::string& node = f.names[u];
+    // LinkMonitor.cpp:1001: published - the increment it carries + the new one
+    const LinkStateMetric delta =
+        static_cast<LinkStateMetric>(inc) - ls.getNodeMetricIncrement(node);
+    for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) {
+      sideMetric(f.edgeLink[e], node) += delta;
+    }
+    const uint8_t add = uint8_t((OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC) & ~f.nodeFlags[u]);
+    if (add) bits[u] |= add;
+  }
+  std::vector<std::pair<uint32_t, uint64_t>> over;
+  for (const auto& [l, mv] : moved) {
+    if (!l->isUp() || killed.count(l)) continue;  // down stays down
+    const LinkStateMetric w = std::max(mv.m[0], mv.m[1]);
+    if (w == l->getMaxMetric()) continue;  // the link's weight stays: a no-op
+    for (const std::string* n : {&l->firstNodeName(), &l->secondNodeName()}) {
+      const uint32_t u = f.id.at(*n);
+      for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) {
+        if (f.edgeLink[e] == l) over.emplace_back(e, w);
+      }
+    }
+  }
+  std::sort(over.begin(), over.end());
+  over.erase(std::unique(over.begin(), over.end()), over.end());
+  for (const auto& [e, w] : over) {
+    x.metricEdges.push_back(e);
+    x.metricVals.push_back(w);
+  }
+  for (const auto& [u, b] : bits) {
+    x.flagNodes.push_back(u);
+    x.flagBits.push_back(b);
+  }
   return x;
 }
 
 LinkFailureSweep::Form LinkFailureSweep::selectForm() const {
   if (exact_) return kTopologyCopies;
-  if (maxDead_ <= kRegisterMax && drainList_.empty() && !forceBitset_) return kRegisterList;
+  if (maxDead_ <= kRegisterMax && drainList_.empty() && !forceBitset_ && !whatif_) {
+    return kRegisterList;
+  }
   return kEdgeBitset;  // launch() falls back to copies when the entry refuses
 }
 
@@ -195,6 +281,26 @@ LinkFailureSweep::LinkFailureSweep(
     deadOff_.push_back(uint32_t(deadList_.size()));
     drainOff_.push_back(uint32_t(drainList_.size()));
     maxDead_ = std::max(maxDead_, uint32_t(x.deadEdges.size()));
+    metricEdge_.insert(metricEdge_.end(), x.metricEdges.begin(), x.metricEdges.end());
+    metricVal_.insert(metricVal_.end(), x.metricVals.begin(), x.metricVals.end());
+    flagNode_.insert(flagNode_.end(), x.flagNodes.begin(), x.flagNodes.end());
+    flagBits_.insert(flagBits_.end(), x.flagBits.begin(), x.flagBits.end());
+    metricOff_.push_back(uint32_t(metricEdge_.size()));
+    flagOff_.push_back(uint32_t(flagNode_.size()));
+    maxMetricList_ = std::max(maxMetricList_, uint32_t(x.metricEdges.size()));
+  }
+  whatif_ = !metricEdge_.empty() ||
+      std::any_of(flagBits_.begin(), flagBits_.end(),
+                  [](uint8_t b) { return (b & ~uint8_t(OGS_NODE_OVERLOADED)) != 0; });
+  // the overrides' own domain guards: a zero / negative weight replays the
+  // extraction order, a weight that pushes max_metric x (N - 1) past the
+  // 32-bit guard needs 64-bit distances -- either way topology copies
+  {
+    const uint64_t n = f.names.empty() ? 0 : f.names.size() - 1;
+    for (const uint64_t w : metricVal_) {
+      if (w == 0 || w > 0xFFFFFFFFull) exact_ = exactOrder_ = true;
+      if (n != 0 && w > 0x7FFFFFFEull / n) exact_ = true;
+    }
   }
   form_ = selectForm();
 
@@ -213,6 +319,17 @@ LinkFailureSweep::LinkFailureSweep(
   if (!drainList_.empty()) {
     dDrainOff_.upload(drainOff_.data(), drainOff_.size());
     dDrainList_.upload(drainList_.data(), drainList_.size());
+  }
+  if (whatif_ && !exact_) {
+    std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());  // all within 32 bits
+    dMetricOff_.upload(metricOff_.data(), metricOff_.size());
+    dMetricEdge_.upload(metricEdge_.data(), metricEdge_.size());
+    dMetricVal_.upload(vals.data(), vals.size());
+    if (!flagNode_.empty()) {
+      dFlagOff_.upload(flagOff_.data(), flagOff_.size());
+      dFlagNode_.upload(flagNode_.data(), flagNode_.size());
+      dFlagBits_.upload(flagBits_.data(), flagBits_.size());
+    }
   }
   {
     const std::vector<uint32_t> cls = advClasses(table_);
@@ -271,6 +388,17 @@ void LinkFailureSweep::exactLaunch(void* stream) {
             if (f.edgeLink[r] == f.edgeLink[e]) hb.edges[e0 + r] |= OGS_EDGE_DST_OVERLOADED;
           }
         }
+      }
+      // metric overrides, as LinkState::patchFlat re-encodes a moved metric,
+      // and the soft-drain bits (link_state.cpp: the node's flags alone)
+      for (uint32_t i = metricOff_[t - 1]; i < metricOff_[t]; ++i) {
+        uint64_t& w = hb.edges[e0 + metricEdge_[i]];
+        w = (w & 0xFFFFFFFFull) | (uint64_t(uint32_t(metricVal_[i])) << 32);
+        hb.maxMetric = std::max(hb.maxMetric, metricVal_[i]);
+        hb.hasZeroMetric |= metricVal_[i] == 0;
+      }
+      for (uint32_t i = flagOff_[t - 1]; i < flagOff_[t]; ++i) {
+        hb.nodeFlags[n0 + flagNode_[i]] |= flagBits_[i];
       }
     }
     std::vector<ogs_unit> us(n);
@@ -381,6 +509,25 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     ogsCheck(ogs_spf_routes_variants(&g, &pt, dUnits_.as<ogs_unit>(), int32_t(numVariants()),
                                      &mods, &diff, fl, W_, &out, stream),
              "ogs_spf_routes_variants");
+  } else if (whatif_) {
+    const bool nodes = !flagNode_.empty(), metrics = !metricEdge_.empty();
+    ogs_whatif_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
+                         nodes ? dFlagOff_.as<uint32_t>() : nullptr,
+                         nodes ? dFlagNode_.as<uint32_t>() : nullptr,
+                         nodes ? dFlagBits_.as<uint8_t>() : nullptr,
+                         metrics ? dMetricOff_.as<uint32_t>() : nullptr,
+                         metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
+                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, maxMetricList_};
+    const int rc = ogs_spf_routes_whatif(&g, &pt, dUnits_.as<ogs_unit>(),
+                                         int32_t(numVariants()), &mods, &diff, fl, W_, &out,
+                                         stream);
+    if (rc == OGS_E_UNSUPPORTED) {
+      // node bits the repair cannot take (kFull mode, W > 1, its LDS budget):
+      // one topology per scenario (nothing was launched)
+      form_ = kTopologyCopies;
+      return exactLaunch(stream);
+    }
+    ogsCheck(rc, "ogs_spf_routes_whatif");
   } else {
     const bool drains = !drainList_.empty();
     ogs_scenario_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),

@@ -482,6 +482,64 @@ int ogs_spf_routes_scenarios(const ogs_graph* graph,
   return e == hipSuccess ? OGS_OK : hipFail(e, "scenario launch");
 }
 
+int ogs_spf_routes_whatif(const ogs_graph* graph,
+                          const ogs_prefix_table* prefixes,
+                          const ogs_unit* units, int32_t n_units,
+                          const ogs_whatif_mods* mods,
+                          ogs_route_diff* diff, uint32_t flags,
+                          int32_t nh_words, ogs_spf_out* out, void* stream) {
+  // the rules shared with ogs_spf_routes_scenarios, in its order
+  if (!graph || !prefixes || !out) return fail(OGS_E_INVALID, "graph/prefixes/out is NULL");
+  if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
+  if (n_units == 0) return OGS_OK;
+  if (!units || !graph->node_base || !graph->row_ptr || !graph->edges ||
+      !graph->node_flags || !prefix_arrays_set(prefixes)) {
+    return fail(OGS_E_INVALID, "graph / prefix table arrays are NULL");
+  }
+  if (!mods || !mods->dead_off || !mods->dead_edges) {
+    return fail(OGS_E_INVALID, "mods, dead_off or dead_edges is NULL");
+  }
+  if (!mods->node_off != !mods->node_ids || !mods->node_off != !mods->node_bits) {
+    return fail(OGS_E_INVALID, "mods: node_off, node_ids and node_bits go together");
+  }
+  if (!mods->metric_off != !mods->metric_edges || !mods->metric_off != !mods->metric_vals) {
+    return fail(OGS_E_INVALID, "mods: metric_off, metric_edges and metric_vals go together");
+  }
+  if (diff && (!diff->base_meta || !diff->base_metric || !diff->base_mask ||
+               !diff->changed || !diff->counts)) {
+    return fail(OGS_E_INVALID, "diff arrays are NULL");
+  }
+  if ((flags & OGS_F_INCREMENTAL) && (!diff || !diff->base_dist || !diff->base_nh)) {
+    return fail(OGS_E_INVALID, "OGS_F_INCREMENTAL needs diff with base_dist / base_nh");
+  }
+  if ((flags & OGS_F_CHANGED_ONLY) && (!(flags & OGS_F_INCREMENTAL) || nh_words != 1)) {
+    return fail(OGS_E_INVALID, "OGS_F_CHANGED_ONLY needs OGS_F_INCREMENTAL and nh_words 1");
+  }
+  if (int rc = check_max_nodes(graph)) return rc;
+  if (nh_words < 1) {
+    return fail(OGS_E_INVALID, "nh_words < 1");
+  }
+  int unsupported = 0;
+  hipError_t e = ogs::launch_whatif(*graph, *prefixes, units, n_units, *mods, diff, flags,
+                                    nh_words, *out, static_cast<hipStream_t>(stream),
+                                    &unsupported);
+  if (unsupported == 1) {
+    return fail(OGS_E_UNSUPPORTED,
+                "what-if lists need the large-topology path (edge_src, nh_words <= 4, "
+                "32-bit distances)");
+  }
+  if (unsupported == 2) {
+    return fail(OGS_E_UNSUPPORTED,
+                "node bits run in the base SPF's repair only: OGS_F_INCREMENTAL, nh_words 1, "
+                "max_nodes <= 65535, bitsets, flag row and metric slice within the LDS budget");
+  }
+  if (unsupported) {
+    return fail(OGS_E_UNSUPPORTED,
+                "the edge bitsets and the metric slice do not fit the LDS of any form");
+  }
+  return e == hipSuccess ? OGS_OK : hipFail(e, "what-if launch");
+}
+
 int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
                              int32_t max_prefixes, const ogs_spf_out* records,
                              int32_t nh_words, const ogs_route_changes* changes,
@@ -674,6 +732,15 @@ int ogs_ctx_spf_routes_scenarios(ogs_ctx* ctx, const ogs_graph* graph,
                                  ogs_spf_out* out, void* stream) {
   OGS_CTX_CALL(ctx, ogs_spf_routes_scenarios(graph, prefixes, units, n_units, mods, diff, flags,
                                              nh_words, out, stream));
+}
+
+int ogs_ctx_spf_routes_whatif(ogs_ctx* ctx, const ogs_graph* graph,
+                              const ogs_prefix_table* prefixes, const ogs_unit* units,
+                              int32_t n_units, const ogs_whatif_mods* mods,
+                              ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
+                              ogs_spf_out* out, void* stream) {
+  OGS_CTX_CALL(ctx, ogs_spf_routes_whatif(graph, prefixes, units, n_units, mods, diff, flags,
+                                          nh_words, out, stream));
 }
 
 int ogs_ctx_ksp_paths(ogs_ctx* ctx, const ogs_graph* graph, const ogs_path_unit* units,

@@ -56,6 +56,13 @@ hipError_t launch_scenarios(const ogs_graph& g, const ogs_prefix_table& pt,
                             const ogs_scenario_mods& mods, ogs_route_diff* diff,
                             uint32_t flags, int W, const ogs_spf_out& out,
                             hipStream_t stream, int* unsupported);
+// *unsupported: 1 and 3 as launch_scenarios (3: the bitsets and the metric
+// slice past every form's LDS), 2 node bits that the repair cannot take
+hipError_t launch_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
+                         const ogs_unit* units, int nUnits,
+                         const ogs_whatif_mods& mods, ogs_route_diff* diff,
+                         uint32_t flags, int W, const ogs_spf_out& out,
+                         hipStream_t stream, int* unsupported);
 // route_multiarea.hip
 hipError_t launch_routes_multiarea(const ogs_graph& g, const ogs_prefix_table& pt,
                                    const ogs_area_table& at,
@@ -174,5 +181,18 @@ hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
                                  uint32_t flags, int W, const ogs_spf_out& out,
                                  const ogs_scenario_mods& mods, const ogs_route_diff* diff,
                                  void* scratch, hipStream_t stream);
+bool whatif_repair_fits(const ogs_graph& g, uint32_t flags, int W, const ogs_route_diff* diff,
+                        bool nodes, uint32_t maxMetric);
+bool whatif_frontier_fits(const ogs_graph& g, uint32_t flags, int W, uint32_t maxMetric);
+hipError_t launch_whatif_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                const uint32_t* key, const ogs_unit* units, int n,
+                                uint32_t flags, const ogs_spf_out& out,
+                                const ogs_whatif_mods& mods, ogs_route_diff* diff,
+                                void* scratch, hipStream_t stream);
+hipError_t launch_frontier_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
+                                  const uint32_t* key, const ogs_unit* units, int n,
+                                  uint32_t flags, int W, const ogs_spf_out& out,
+                                  const ogs_whatif_mods& mods, const ogs_route_diff* diff,
+                                  void* scratch, hipStream_t stream);
 
 }  // namespace ogs

@@ -261,6 +261,58 @@ hipError_t launch_scenarios(const ogs_graph& g, const ogs_prefix_table& pt,
                                stream);
 }
 
+// ogs_spf_routes_whatif: launch_scenarios' preamble and choice over lists that
+// also carry node bits and metric overrides.
+hipError_t launch_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
+                         const ogs_unit* units, int nUnits,
+                         const ogs_whatif_mods& mods, ogs_route_diff* diff,
+                         uint32_t flags, int W, const ogs_spf_out& out,
+                         hipStream_t stream, int* unsupported) {
+  if (!g.edge_src || (flags & OGS_F_WIDE_METRIC) || !frontier_fits(g, flags, W) ||
+      (W != 1 && W != 2 && W != 4)) {
+    *unsupported = 1;
+    return hipSuccess;
+  }
+  const bool nodes = mods.node_off != nullptr;
+  const uint32_t maxMetric = mods.metric_off ? mods.max_metric_per_unit : 0u;
+  const bool repair = whatif_repair_fits(g, flags, W, diff, nodes, maxMetric);
+  if (!repair && nodes) {
+    *unsupported = 2;
+    return hipSuccess;
+  }
+  if (!repair && !whatif_frontier_fits(g, flags, W, maxMetric)) {
+    *unsupported = 3;
+    return hipSuccess;
+  }
+  ogs_whatif_mods m = mods;
+  m.max_metric_per_unit = maxMetric;
+  const size_t Sp = size_t(pt.max_prefixes);
+  const size_t keyBytes = round256(size_t(g.num_topos) * Sp * 4);
+  void* ws = nullptr;
+  // after the keys: the repair's descendant rows or the full form's chunk lists
+  hipError_t e = workspace(keyBytes + std::max(chunk_scratch_bytes(g), desc_scratch_bytes(g)),
+                           stream, &ws);
+  if (e != hipSuccess) return e;
+  uint32_t* key = static_cast<uint32_t*>(ws);
+  if (diff) {
+    e = hipMemsetAsync(diff->changed, 0, size_t(nUnits) * ((Sp + 31) / 32) * 4, stream);
+    if (e != hipSuccess) return e;
+  }
+  if (Sp > 0) {
+    hipLaunchKernelGGL(pfx_key_kernel, dim3(unsigned((Sp + kBlock - 1) / kBlock),
+                                            unsigned(g.num_topos)),
+                       dim3(kBlock), 0, stream, pt, g.num_topos, key);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  void* scratch = static_cast<char*>(ws) + keyBytes;
+  if (repair) {
+    return launch_whatif_repair(g, pt, key, units, nUnits, flags, out, m, diff, scratch, stream);
+  }
+  return launch_frontier_whatif(g, pt, key, units, nUnits, flags, W, out, m, diff, scratch,
+                                stream);
+}
+
 // Large shared topologies with a prefix table: key fold, then either the
 // fused frontier SPF + stream launch (route_stream 2), or an SPF launch
 // (frontier / multi-source sweep) and a route-stream launch (route_stream 1).

@@ -121,6 +121,10 @@ struct DeadEdges {
     for (int k = 0; k < kMaxDead; ++k) d |= x == e[k];
     return d;
   }
+  // edge e's weight (x = its CSR word): these lists move no metric
+  __device__ __forceinline__ uint32_t weight(uint32_t, uint64_t x) const {
+    return static_cast<uint32_t>(x >> 32);
+  }
 };
 
 // Dead edges of a what-if scenario (ogs_scenario_mods): a list of any length,
@@ -130,6 +134,36 @@ struct DeadBits {
   const uint32_t* bits;  // LDS [ceil(E/32)]
   __device__ __forceinline__ bool has(uint32_t x) const {
     return (bits[x >> 5] >> (x & 31u)) & 1u;
+  }
+  __device__ __forceinline__ uint32_t weight(uint32_t, uint64_t x) const {
+    return static_cast<uint32_t>(x >> 32);
+  }
+};
+
+// Edge mods of a what-if unit (ogs_whatif_mods): "is e dead" and "what is e's
+// weight". One LDS u64 per 32 edges holds {dead word, overridden word}, so an
+// edge that is neither costs one 8-byte LDS read, as DeadBits::has costs one
+// word; an overridden edge finds its weight by binary search in the unit's
+// slice (edge ids ascending), copied to LDS. The search stays inside [0, n)
+// whatever the slice holds.
+struct WhatifBits {
+  const uint64_t* bb;   // LDS [ceil(E/32) (+ 1)]: dead | overridden << 32
+  const uint32_t* me;   // LDS [n] overridden edge ids, ascending
+  const uint32_t* mv;   // LDS [n] their weights
+  uint32_t n;
+  __device__ __forceinline__ bool has(uint32_t x) const {
+    return (static_cast<uint32_t>(bb[x >> 5]) >> (x & 31u)) & 1u;
+  }
+  __device__ __forceinline__ uint32_t weight(uint32_t e, uint64_t x) const {
+    if (!((static_cast<uint32_t>(bb[e >> 5] >> 32) >> (e & 31u)) & 1u)) {
+      return static_cast<uint32_t>(x >> 32);
+    }
+    uint32_t lo = 0, hi = n;  // n >= 1: a set bit came from the slice
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (me[mid] <= e) lo = mid; else hi = mid;
+    }
+    return mv[lo];
   }
 };
 
@@ -144,6 +178,9 @@ __device__ __forceinline__ void load_chunk(const uint64_t* __restrict__ edges,
     x[i] = i < n ? edges[b + i] : uint64_t(OGS_EDGE_DOWN);
     if constexpr (MODS) {
       if (dead.has(b + i)) x[i] |= uint64_t(OGS_EDGE_DOWN);
+      if constexpr (std::is_same_v<Dead, WhatifBits>) {
+        if (i < n) x[i] = (x[i] & 0xFFFFFFFFull) | (uint64_t(dead.weight(b + i, x[i])) << 32);
+      }
     }
   }
 }
@@ -269,7 +306,7 @@ __device__ __forceinline__ void frontier_spf(
         if (dead.has(b + j)) continue;
       }
       const uint32_t t = edge_dst(lo);
-      const uint32_t c = hop ? 1u : static_cast<uint32_t>(x >> 32);
+      const uint32_t c = hop ? 1u : dead.weight(b + j, x);
       if (c < dist[t]) {
         atomicMin(&dist[t], c);
         stamp[t] = 2;
@@ -328,7 +365,7 @@ __device__ __forceinline__ void frontier_spf(
         if (dead.has(b + j)) continue;
       }
       const uint32_t t = edge_dst(lo);
-      const uint32_t w = hop ? 1u : static_cast<uint32_t>(x >> 32);
+      const uint32_t w = hop ? 1u : dead.weight(b + j, x);
       if (w == dist[t]) {
         atomicOr(&nh[t * W + (j >> 5)], 1u << (j & 31u));
         stamp[t] = uint16_t(r0);
@@ -427,7 +464,7 @@ __device__ __forceinline__ void frontier_spf_packed(
         if (dead.has(sb + j)) continue;
       }
       const uint32_t t = edge_dst(lo);
-      const uint32_t c = hop ? 1u : static_cast<uint32_t>(x >> 32);
+      const uint32_t c = hop ? 1u : dead.weight(sb + j, x);
       const uint32_t bits = j < 32u ? 1u << j : 0u;
       uint64_t old = dn[t];
       for (;;) {
@@ -594,7 +631,7 @@ __device__ __forceinline__ void queue_spf(
           if (dead.has(e)) return;
         }
         const uint32_t t = edge_dst(lo);
-        const uint32_t c = dv + (hop ? 1u : static_cast<uint32_t>(x >> 32));
+        const uint32_t c = dv + (hop ? 1u : dead.weight(e, x));
         if (c < dist[t] && c < atomicMin(&dist[t], c)) append(t, r);
       });
     }
@@ -620,7 +657,7 @@ __device__ __forceinline__ void queue_spf(
         if (dead.has(b + j)) continue;
       }
       const uint32_t t = edge_dst(lo);
-      const uint32_t w = hop ? 1u : static_cast<uint32_t>(x >> 32);
+      const uint32_t w = hop ? 1u : dead.weight(b + j, x);
       if (w == dist[t]) {
         atomicOr(&nh[t * W + (j >> 5)], 1u << (j & 31u));
         append(t, r0);
@@ -651,7 +688,7 @@ __device__ __forceinline__ void queue_spf(
           if (dead.has(e)) return;
         }
         const uint32_t t = edge_dst(lo);
-        if (dv + (hop ? 1u : static_cast<uint32_t>(x >> 32)) != dist[t]) return;
+        if (dv + (hop ? 1u : dead.weight(e, x)) != dist[t]) return;
         bool add = false;
 #pragma unroll
         for (int k = 0; k < W; ++k) {
@@ -713,7 +750,7 @@ __device__ __forceinline__ uint32_t packed_rounds(
           if (dead.has(e)) return;
         }
         const uint32_t t = edge_dst(lo);
-        const uint32_t c = dv + (hop ? 1u : static_cast<uint32_t>(x >> 32));
+        const uint32_t c = dv + (hop ? 1u : dead.weight(e, x));
         // the source contributes the link slot (its row index), others NH(v)
         const uint32_t bits = (v == s) ? (1u << (e - b)) : nv;
         uint64_t old = dn[t];
@@ -816,7 +853,9 @@ __device__ uint32_t g_diagStamps[kDiagWgs * 8];
 // rank's shard of the C3 sources) so keeps enough waves streaming per CU.
 // Mods = ogs_scenario_mods (MODS): the unit's dead list of any length in an
 // LDS bitset at smem + bitsOff (DeadBits), built by this workgroup -- each of
-// a unit's `parts` workgroups builds its own.
+// a unit's `parts` workgroups builds its own. Mods = ogs_whatif_mods: the dead
+// and the "overridden" bitset interleaved and the unit's (edge, weight) slice
+// there (WhatifBits); a unit with a bad weight is refused before its SPF.
 template <int W, bool ROUTES, bool MODS, bool DIFF, int QMODE, bool OUTS3, int B = kBlock,
           typename Mods = ogs_unit_mods>
 __device__ __forceinline__ void spf_frontier_body(
@@ -827,7 +866,8 @@ __device__ __forceinline__ void spf_frontier_body(
     const Mods& mods, const ogs_route_diff& diff, uint32_t parts, uint32_t bitsOff = 0u) {
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   constexpr bool LIST = std::is_same_v<Mods, ogs_scenario_mods>;
-  static_assert(!LIST || MODS, "a scenario list is a MODS form");
+  constexpr bool WHATIF = std::is_same_v<Mods, ogs_whatif_mods>;
+  static_assert(!(LIST || WHATIF) || MODS, "a scenario list is a MODS form");
   const int tid = threadIdx.x;
   static_assert(B == kBlock || (OUTS3 && !MODS && !DIFF && (QMODE == 0 || QMODE == 4)),
                 "other block sizes only for the all-sources stream");
@@ -855,8 +895,49 @@ __device__ __forceinline__ void spf_frontier_body(
       : reinterpret_cast<uint32_t*>(q1 + ((Sn + 1u) & ~1u));
   __shared__ uint32_t qcnt[3];
 
-  std::conditional_t<LIST, DeadBits, DeadEdges> dead;
-  if constexpr (!LIST) {
+  std::conditional_t<WHATIF, WhatifBits, std::conditional_t<LIST, DeadBits, DeadEdges>> dead;
+  if constexpr (WHATIF) {
+    // [list_bits_words(g)] u64 {dead, overridden}, then the slice's ids and weights
+    uint64_t* bb = reinterpret_cast<uint64_t*>(smem + bitsOff);
+    uint32_t* bb32 = reinterpret_cast<uint32_t*>(bb);
+    uint32_t* me = bb32 + 2u * ((uint32_t(g.max_edges) + 31u) / 32u + 1u);
+    uint32_t* mv = me + mods.max_metric_per_unit;
+    const uint32_t E = gRow[N] - e0;
+    __shared__ uint32_t refused;
+    // (under OGS_F_HOP_METRIC the metric lists are ignored)
+    const bool metrics = mods.metric_off && !(flags & OGS_F_HOP_METRIC);
+    const uint32_t m0 = metrics ? mods.metric_off[u0] : 0u;
+    const uint32_t mn = metrics ? mods.metric_off[u0 + 1] - m0 : 0u;
+    const bool tooLong = mn > mods.max_metric_per_unit;  // past the LDS the caller sized
+    // (one word past E's in both bitsets: load_chunk tests up to kChunk - 1 ids
+    // past a row's end)
+    for (uint32_t w = tid; w < (E + 31u) / 32u + 1u; w += B) bb[w] = 0ull;
+    if (tid == 0) refused = tooLong ? 1u : 0u;
+    __syncthreads();
+    for (uint32_t i = mods.dead_off[u0] + tid; i < mods.dead_off[u0 + 1]; i += B) {
+      const uint32_t e = mods.dead_edges[i];
+      if (e < E) atomicOr(&bb32[2u * (e >> 5)], 1u << (e & 31u));
+    }
+    for (uint32_t i = tid; !tooLong && i < mn; i += B) {
+      const uint32_t e = mods.metric_edges[m0 + i], v = mods.metric_vals[m0 + i];
+      me[i] = e;
+      mv[i] = v;
+      if (e >= E) continue;  // skipped: sets no bit, so the search never returns it
+      if (v - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
+        refused = 1u;
+        continue;
+      }
+      atomicOr(&bb32[2u * (e >> 5) + 1u], 1u << (e & 31u));
+    }
+    __syncthreads();
+    if (refused) {  // unit-uniform: no SPF, no record, the zeroed `changed` row
+      if constexpr (DIFF) {
+        if (tid < 2) diff.counts[size_t(u0) * 2 + tid] = OGS_WHATIF_REFUSED;
+      }
+      return;
+    }
+    dead = WhatifBits{bb, me, mv, mn};
+  } else if constexpr (!LIST) {
 #pragma unroll
     for (int k = 0; k < kMaxDead; ++k) {
       dead.e[k] = (MODS && k < mods.dead_per_unit)
@@ -1013,9 +1094,31 @@ __global__ __launch_bounds__(kBlock) void spf_frontier_list_kernel(
                                                                mods, diff, 1u, bitsOff);
 }
 
+// ogs_spf_routes_whatif without the repair: dead and overridden bitsets and the
+// unit's metric slice after the SPF state; every row walk reads the
+// overridden weight (a lowered metric is ordinary in a recompute from scratch)
+template <int W, bool DIFF, int QMODE>
+__global__ __launch_bounds__(kBlock) void spf_frontier_whatif_kernel(
+    ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
+    const uint64_t* __restrict__ chunks, const uint32_t* __restrict__ nChunk,
+    uint32_t cap, const ogs_unit* __restrict__ units, uint32_t flags,
+    uint32_t* __restrict__ oDist, uint32_t* __restrict__ oNh, ogs_spf_out out,
+    ogs_whatif_mods mods, ogs_route_diff diff, uint32_t bitsOff) {
+  spf_frontier_body<W, true, true, DIFF, QMODE, false, kBlock>(g, pt, key, chunks, nChunk, cap,
+                                                               units, flags, oDist, oNh, out,
+                                                               mods, diff, 1u, bitsOff);
+}
+
 // words of the list forms' dead bitset (one past the edges': see the body)
 __host__ __device__ inline uint32_t list_bits_words(const ogs_graph& g) {
   return (uint32_t(g.max_edges) + 31u) / 32u + 1u;
+}
+// static LDS of the what-if full form's kernels: at most 272 B (the chunk-scan
+// instantiations: tile-scan sums, list counts, the refused flag), rounded up
+constexpr uint32_t kWhatifStaticLds = 288u;
+// bytes the what-if full form adds after the SPF state (8-aligned start)
+__host__ __device__ inline uint32_t whatif_extra_bytes(const ogs_graph& g, uint32_t maxMetric) {
+  return 8u + 8u * list_bits_words(g) + 8u * maxMetric;
 }
 
 // "spf_seed_row" option: 1 (default) round 1 of the chunk-scan forms relaxes
@@ -1076,6 +1179,13 @@ hipError_t launch_frontier_q(const ogs_graph& g, const ogs_prefix_table& pt,
     return launch_dyn_lds(spf_frontier_list_kernel<W, DIFF, QMODE>, dim3(unsigned(nUnits)),
                           dim3(B), lds + 4u * list_bits_words(g), stream, g, pt, key, chunks,
                           nChunk, chunk_cap(g), units, flags, dist, nh, out, mods, diff, lds);
+  } else if constexpr (std::is_same_v<Mods, ogs_whatif_mods>) {
+    static_assert(ROUTES && MODS && !OUTS3 && B == kBlock, "the list form is a variants form");
+    const uint32_t off = (lds + 7u) & ~7u;
+    return launch_dyn_lds(spf_frontier_whatif_kernel<W, DIFF, QMODE>, dim3(unsigned(nUnits)),
+                          dim3(B), off + whatif_extra_bytes(g, mods.max_metric_per_unit) - 8u,
+                          stream, g, pt, key, chunks, nChunk, chunk_cap(g), units, flags, dist,
+                          nh, out, mods, diff, off);
   } else {
     return launch_dyn_lds(spf_frontier_kernel<W, ROUTES, MODS, DIFF, QMODE, OUTS3, B>,
                           dim3(unsigned(nUnits) * unsigned(parts)), dim3(B), lds, stream, g, pt,
@@ -1166,6 +1276,12 @@ hipError_t launch_frontier(const ogs_graph& g, const ogs_prefix_table& pt,
     // the queue forms' lists and the bitset together past the CU's LDS: chunk scan
     if (frontier_lds_bytes(uint32_t(g.max_nodes), W, true) + 4u * list_bits_words(g) + 64u >
         160u * 1024u) {
+      qm = 0;
+    }
+  }
+  if constexpr (std::is_same_v<Mods, ogs_whatif_mods>) {
+    if (frontier_lds_bytes(uint32_t(g.max_nodes), W, true) +
+            whatif_extra_bytes(g, mods.max_metric_per_unit) + kWhatifStaticLds > 160u * 1024u) {
       qm = 0;
     }
   }
@@ -1408,6 +1524,22 @@ uint32_t repair_lds_bytes(uint32_t Sn) {
 // DAG can move: the seeds are the heads of x's base-tight out-edges. x's own
 // routes change through the flag alone (DRAINED, route selection), so the
 // changed-only route pass also visits prefixes x advertises.
+// WHATIF (ogs_spf_routes_whatif, a LIST form): ogs_whatif_mods. DRAINS then
+// says "the call carries node bits": the flag row takes each listed node's
+// bits, OGS_NODE_OVERLOADED seeding as above, the soft-drain bits changing
+// route selection only (the node joins the prefix pass). The dead and the
+// "overridden" bitset are interleaved (WhatifBits) and the unit's metric slice
+// is copied to LDS; the fill pass classifies each override against the CSR
+// weight: raised and base-tight -> seedOf, exactly as a dead edge (the head's
+// base paths through it are gone, every other node keeps a path no longer
+// than before, so A and its boundary are right and the rounds below read the
+// new weights); raised and not tight, or equal -> nothing; lowered -> the unit
+// cannot be repaired from below (nodes OUTSIDE any base descendant set get
+// shorter paths) and recomputes from the source in place: dn = infinity but
+// the source, the list = {source}, the same packed rounds -- queue_spf_packed's
+// start state over the arrays the repair already holds -- and inA all ones, so
+// the changed-only pass compares every prefix; 0 or >= 2^31 -> refused.
+// (the statements: spf_repair_body.h)
 template <bool CHANGED_ONLY, bool LIST = false, bool DRAINS = false>
 __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
     ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
@@ -1415,263 +1547,23 @@ __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(
     uint32_t* __restrict__ oNh, ogs_spf_out out,
     std::conditional_t<LIST, ogs_scenario_mods, ogs_unit_mods> mods,
     ogs_route_diff diff, const uint32_t* __restrict__ desc) {
-  static_assert(LIST || !DRAINS, "drains come with the list form");
-  constexpr uint32_t kInf = 0xFFFFFFFFu;
-  const int tid = threadIdx.x;
-  const uint32_t u0 = blockIdx.x;
-  const ogs_unit unit = units[u0];
-  const uint32_t s = unit.src;
-  const uint32_t nb = g.node_base[unit.topo];
-  const uint32_t N = g.node_base[unit.topo + 1] - nb;
-  const uint32_t* __restrict__ gRow = g.row_ptr + nb;
-  const uint32_t e0 = gRow[0];
-  const uint64_t* __restrict__ edges = g.edges + e0;
-  const uint8_t* gflags = g.node_flags + nb;  // the base's
-  const uint32_t Sn = uint32_t(g.max_nodes);
-  const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
-  const uint32_t* __restrict__ bD = diff.base_dist;
-  const uint32_t* __restrict__ bN = diff.base_nh;
+  constexpr bool WHATIF = false;
+#include "spf_repair_body.h"
+}
 
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint64_t* dn = reinterpret_cast<uint64_t*>(smem);                      // [Sn]
-  uint32_t* stamp = reinterpret_cast<uint32_t*>(dn + Sn);                // [Sn]
-  uint16_t* q0 = reinterpret_cast<uint16_t*>(stamp + ((Sn + 3u) & ~3u));  // [Sn]
-  uint16_t* q1 = q0 + ((Sn + 1u) & ~1u);                                 // [Sn]
-  uint32_t* inA = reinterpret_cast<uint32_t*>(q1 + ((Sn + 1u) & ~1u));   // [Sn/32]
-  __shared__ uint32_t qcnt[3], cnt[2];
-  auto isA = [&](uint32_t v) { return (inA[v >> 5] >> (v & 31u)) & 1u; };
-  // LIST: the unit's slices, the bitset [ceil(max_edges/32)] and the flag row
-  uint32_t l0 = 0, l1 = 0, r0 = 0, r1 = 0, E = 0;
-  uint32_t* deadBits = nullptr;
-  uint8_t* lflags = nullptr;
-  if constexpr (LIST) {
-    l0 = mods.dead_off[u0];
-    l1 = mods.dead_off[u0 + 1];
-    E = gRow[N] - e0;
-    deadBits = inA + (Sn + 31u) / 32u;
-    if constexpr (DRAINS) {
-      r0 = mods.drain_off[u0];
-      r1 = mods.drain_off[u0 + 1];
-      lflags = reinterpret_cast<uint8_t*>(deadBits + (uint32_t(g.max_edges) + 31u) / 32u);
-    }
-  }
-  const bool drains = DRAINS && r1 > r0;  // unit-uniform
-  // (the drained row is written above the seeds: no restrict on it)
-  typedef const uint8_t* __restrict__ FlagsRestrict;
-  std::conditional_t<DRAINS, const uint8_t*, FlagsRestrict> nflags = drains ? lflags : gflags;
-  // the base's tight DAG (seeds, growth rounds) is told by the base's flags
-  auto relaxesBase = [&](uint32_t v) { return v == s || !(gflags[v] & OGS_NODE_OVERLOADED); };
-  auto relaxes = [&](uint32_t v) { return v == s || !(nflags[v] & OGS_NODE_OVERLOADED); };
-  auto seed = [&](uint32_t v) {
-    if (!(atomicOr(&inA[v >> 5], 1u << (v & 31u)) & (1u << (v & 31u)))) {
-      q1[atomicAdd(&qcnt[1], 1u)] = uint16_t(v);
-    }
-  };
-  // head of dead edge e when the edge is tight in the base
-  auto seedOf = [&](uint32_t e) {
-    const uint32_t u = g.edge_src[e0 + e];
-    const uint64_t x = edges[e];
-    const uint32_t lo = static_cast<uint32_t>(x);
-    const uint32_t v = edge_dst(lo);
-    const uint32_t w = hop ? 1u : static_cast<uint32_t>(x >> 32);
-    if (!(lo & OGS_EDGE_DOWN) && relaxesBase(u) && bD[u] != kInf && bD[u] + w == bD[v]) seed(v);
-  };
-
-  std::conditional_t<LIST, DeadBits, DeadEdges> dead;
-  if constexpr (!LIST) {
-#pragma unroll
-    for (int k = 0; k < kMaxDead; ++k) {
-      dead.e[k] = k < mods.dead_per_unit ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + k]
-                                         : OGS_NODE_NONE;
-    }
-  } else {
-    dead.bits = deadBits;
-    for (uint32_t w = tid; w < (E + 31u) / 32u; w += kBlock) deadBits[w] = 0u;
-    if (drains) {
-      for (uint32_t v = tid; v < N; v += kBlock) lflags[v] = gflags[v];
-    }
-  }
-  for (uint32_t w = tid; w < (N + 31u) / 32u; w += kBlock) inA[w] = 0u;
-  if (tid < 3) qcnt[tid] = 0u;
-  if (tid < 2) cnt[tid] = 0u;
-  __syncthreads();
-  // ---- seeds: heads of the failed edges that are tight in the base --------
-  if constexpr (!LIST) {
-    // (the seed's edge straight from the list: indexing `dead` by tid would put
-    // the array in scratch memory, and every edge test of the rounds with it)
-    const uint32_t seedEdge = (tid < kMaxDead && tid < mods.dead_per_unit)
-        ? mods.dead_edges[size_t(u0) * mods.dead_per_unit + tid]
-        : OGS_NODE_NONE;
-    if (seedEdge != OGS_NODE_NONE) seedOf(seedEdge);
-  } else {
-    for (uint32_t i = l0 + tid; i < l1; i += kBlock) {
-      const uint32_t e = mods.dead_edges[i];
-      if (e >= E) continue;  // OGS_NODE_NONE or a bad id: never outside the bitset
-      atomicOr(&deadBits[e >> 5], 1u << (e & 31u));
-      seedOf(e);
-    }
-    // a drained node's strict descendants: heads of its base-tight out-edges
-    // (not the source, which always relaxes; reached; not drained already)
-    for (uint32_t i = r0 + tid; DRAINS && i < r1; i += kBlock) {
-      const uint32_t x = mods.drain_nodes[i];
-      if (x >= N) continue;
-      const uint8_t fx = gflags[x];
-      lflags[x] = fx | OGS_NODE_OVERLOADED;
-      const uint32_t dx = bD[x];
-      if (x == s || (fx & OGS_NODE_OVERLOADED) || dx == kInf) continue;
-      const uint32_t b = gRow[x] - e0;
-      for_row(edges, b, gRow[x + 1] - e0 - b, [&](uint32_t, uint64_t y) {
-        const uint32_t lo = static_cast<uint32_t>(y);
-        if (lo & OGS_EDGE_DOWN) return;
-        const uint32_t t = edge_dst(lo);
-        if (dx + (hop ? 1u : static_cast<uint32_t>(y >> 32)) == bD[t]) seed(t);
-      });
-    }
-  }
-  __syncthreads();
-  uint32_t n = qcnt[1];
-  // (a unit that drains changes its drained nodes' own routes whatever n)
-  if (CHANGED_ONLY && n == 0 && !drains) {  // no failed link on a shortest path: no change
-    if (tid < 2) diff.counts[size_t(u0) * 2 + tid] = 0u;
-    if (oDist || oNh) {
-      for (uint32_t v = tid; v < N; v += kBlock) {
-        if (oDist) oDist[size_t(u0) * Sn + v] = bD[v];
-        if (oNh) oNh[size_t(u0) * Sn + v] = bN[v];
-      }
-    }
-    return;
-  }
-  for (uint32_t v = tid; v < N; v += kBlock) {
-    dn[v] = uint64_t(bD[v]) | (uint64_t(bN[v]) << 32);
-    stamp[v] = 0u;
-  }
-  if (desc) {  // ---- A = OR of the seeds' precomputed descendant rows ------
-    const uint32_t words = (N + 31u) / 32u;
-    for (uint32_t w = tid; w < words; w += kBlock) {
-      uint32_t a = 0u;
-      for (uint32_t i = 0; i < n; ++i) a |= desc[size_t(q1[i]) * words + w];
-      inA[w] = a;
-    }
-    n = 0;
-  }
-  __syncthreads();
-  // ---- A: the seeds' descendants in the base tight DAG (list rounds) ------
-  for (uint32_t r = 1; n; ++r) {
-    if (tid == 0) qcnt[(r + 2) % 3] = 0u;
-    const uint16_t* cur = (r & 1) ? q1 : q0;
-    uint16_t* nxt = (r & 1) ? q0 : q1;
-    for (uint32_t i = tid; i < n; i += kBlock) {
-      const uint32_t x = cur[i];
-      if (!relaxesBase(x)) continue;
-      const uint32_t dx = static_cast<uint32_t>(dn[x]);
-      const uint32_t b = gRow[x] - e0;
-      for_row(edges, b, gRow[x + 1] - e0 - b, [&](uint32_t, uint64_t y) {
-        const uint32_t lo = static_cast<uint32_t>(y);
-        if (lo & OGS_EDGE_DOWN) return;
-        const uint32_t t = edge_dst(lo);
-        if (dx + (hop ? 1u : static_cast<uint32_t>(y >> 32)) != static_cast<uint32_t>(dn[t])) {
-          return;
-        }
-        if (!(atomicOr(&inA[t >> 5], 1u << (t & 31u)) & (1u << (t & 31u)))) {
-          nxt[atomicAdd(&qcnt[(r + 1) % 3], 1u)] = uint16_t(t);
-        }
-      });
-    }
-    __syncthreads();
-    n = qcnt[(r + 1) % 3];
-  }
-  // ---- reset A, seed its boundary, re-relax --------------------------------
-  __syncthreads();  // every thread has read the last (zero) count
-  if (tid < 3) qcnt[tid] = 0u;
-  for (uint32_t v = tid; v < N; v += kBlock) {
-    if (isA(v)) dn[v] = uint64_t(kInf);
-  }
-  __syncthreads();
-  for (uint32_t x = tid; x < N; x += kBlock) {
-    if (!isA(x)) continue;
-    const uint32_t b = gRow[x] - e0, m = gRow[x + 1] - e0 - b;
-    for (uint32_t j = 0; j < m; ++j) {  // links are two-way: out-neighbours = in-neighbours
-      const uint32_t p = edge_dst(static_cast<uint32_t>(edges[b + j]));
-      if (isA(p) || !relaxes(p) || static_cast<uint32_t>(dn[p]) == kInf) continue;
-      if (atomicMax(&stamp[p], 1u) < 1u) q1[atomicAdd(&qcnt[1], 1u)] = uint16_t(p);
-    }
-  }
-  __syncthreads();
-  packed_rounds<true>(s, edges, gRow, e0, nflags, hop, dn, stamp, q0, q1, qcnt,
-                             nullptr, dead, 1u, qcnt[1]);
-  // from here inA only selects the prefixes the changed-only pass visits:
-  // those of the unit's drained nodes join it
-  if constexpr (DRAINS) {
-    for (uint32_t i = r0 + tid; i < r1; i += kBlock) {
-      const uint32_t x = mods.drain_nodes[i];
-      if (x < N) atomicOr(&inA[x >> 5], 1u << (x & 31u));
-    }
-  }
-  __syncthreads();
-  if (oDist || oNh) {
-    for (uint32_t v = tid; v < N; v += kBlock) {
-      if (oDist) oDist[size_t(u0) * Sn + v] = static_cast<uint32_t>(dn[v]);
-      if (oNh) oNh[size_t(u0) * Sn + v] = static_cast<uint32_t>(dn[v] >> 32);
-    }
-  }
-
-  // ---- routes --------------------------------------------------------------
-  const uint32_t Sp = uint32_t(pt.max_prefixes);
-  const uint32_t p0 = pt.pfx_base[unit.topo];
-  const uint32_t P = pt.pfx_base[unit.topo + 1] - p0;
-  const RouteCfg cfg{(flags & OGS_F_ENABLE_V4) != 0, (flags & OGS_F_V4_OVER_V6) != 0,
-                     (flags & OGS_F_BEST_ROUTE_SELECTION) != 0};
-  const DiffCtx dc{diff.base_meta, diff.base_metric, diff.base_mask,
-                   diff.changed + size_t(u0) * ((Sp + 31u) / 32u), cnt, pt.adv_off + p0,
-                   diff.adv_class};
-  const uint32_t* tkey = key + size_t(unit.topo) * Sp;
-  auto nodeRec = [&](uint32_t v, Rec<1>& r) {
-    const uint64_t x = dn[v];
-    const uint32_t d = static_cast<uint32_t>(x), nv = static_cast<uint32_t>(x >> 32);
-    r.meta = node_route_meta(v, s, d != kInf, __popc(nv), nflags[v]);
-    r.metric = (v == s) ? kInf : d;
-    r.mask[0] = nv;
-  };
-  if constexpr (!CHANGED_ONLY) {
-    stream_routes<1, true>(pt, tkey, p0, P, Sp, u0, s, nflags, PackedView{dn}, cfg, out,
-                           nodeRec, &dc, (flags & kFlagNtStores) != 0);
-  } else {
-    const bool v4Gated = !cfg.enableV4 && !cfg.v4OverV6;
-    uint32_t upd = 0, del = 0;
-    for (uint32_t p = tid; p < P; p += kBlock) {
-      const uint32_t k = tkey[p];
-      bool hit = false;
-      if (!(k & kKeySlow)) {
-        hit = isA(k & kKeyNode);
-      } else {
-        for (uint32_t a = pt.adv_off[p0 + p]; a < pt.adv_off[p0 + p + 1]; ++a) {
-          const uint32_t v = pt.adv_node[a];
-          hit |= v != OGS_NODE_NONE && isA(v);
-        }
-      }
-      if (!hit) continue;  // every advertiser keeps its base state
-      Rec<1> r;
-      if (!(k & kKeySlow)) {
-        if ((k & kKeyV4) && v4Gated) continue;  // the gate's record never changes
-        nodeRec(k & kKeyNode, r);
-        r.sel = (r.meta & OGS_ROUTE_SELECTED) ? 1u : 0u;
-      } else {
-        route_one<uint32_t, 1>(pt, p0 + p, s, nflags, PackedView{dn}, cfg, r.meta, r.metric,
-                               r.mask, r.sel);
-      }
-      if (!route_changed<1>(r, dc, Sp, p, upd, del)) continue;
-      atomicOr(dc.changed + p / 32u, 1u << (p % 32u));
-      const size_t o = size_t(u0) * Sp + p;
-      if (out.meta) out.meta[o] = r.meta;
-      if (out.metric) static_cast<uint32_t*>(out.metric)[o] = r.metric;
-      if (out.sel) out.sel[o] = r.sel;
-      if (out.mask) out.mask[o] = r.mask[0];
-    }
-    if (upd) atomicAdd(&cnt[0], upd);
-    if (del) atomicAdd(&cnt[1], del);
-  }
-  __syncthreads();
-  if (tid < 2) diff.counts[size_t(u0) * 2 + tid] = cnt[tid];
+// ogs_spf_routes_whatif's repair; NODES: the call carries node bits. (Mods is
+// a parameter so that the statements' branches for the other list types stay
+// dependent, i.e. discarded without being checked against ogs_whatif_mods.)
+template <bool CHANGED_ONLY, bool NODES, typename Mods = ogs_whatif_mods>
+__global__ __launch_bounds__(kBlock) void spf_whatif_repair_kernel(
+    ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
+    const ogs_unit* __restrict__ units, uint32_t flags, uint32_t* __restrict__ oDist,
+    uint32_t* __restrict__ oNh, ogs_spf_out out, Mods mods, ogs_route_diff diff,
+    const uint32_t* __restrict__ desc) {
+  constexpr bool WHATIF = std::is_same_v<Mods, ogs_whatif_mods>;
+  static_assert(WHATIF, "the what-if repair takes ogs_whatif_mods");
+  constexpr bool LIST = WHATIF, DRAINS = NODES;
+#include "spf_repair_body.h"
 }
 
 // The base's tight-DAG descendant rows for a repair launch (every unit shares
@@ -1725,6 +1617,42 @@ hipError_t launch_scenarios_repair(const ogs_graph& g, const ogs_prefix_table& p
                        : (drains ? spf_variant_repair_kernel<false, true, true>
                                  : spf_variant_repair_kernel<false, true, false>);
   uint32_t* desc = repair_desc_rows(g, units, flags, diff, scratch, stream, err);
+  if (e != hipSuccess) return e;
+  return launch_dyn_lds(k, dim3(n), dim3(kBlock), lds, stream, g, pt, key, units,
+                        flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
+                        static_cast<uint32_t*>(out.dist), out.nh, out, mods, *diff,
+                        static_cast<const uint32_t*>(desc));
+}
+
+// LDS of the what-if repair: the scenario repair's + the "overridden" words
+// + the unit's metric slice (+ alignment of the interleaved bitsets)
+uint32_t whatif_lds_bytes(const ogs_graph& g, bool nodes, uint32_t maxMetric) {
+  return scenario_lds_bytes(g, nodes) + 4u * ((uint32_t(g.max_edges) + 31u) / 32u) +
+      8u * maxMetric + 8u;
+}
+
+bool whatif_repair_fits(const ogs_graph& g, uint32_t flags, int W, const ogs_route_diff* diff,
+                        bool nodes, uint32_t maxMetric) {
+  return (flags & OGS_F_INCREMENTAL) && diff && diff->base_dist && diff->base_nh && W == 1 &&
+      g.max_nodes <= 65535 && maxMetric <= (1u << 14) &&
+      whatif_lds_bytes(g, nodes, maxMetric) + kRepairStaticLds <= 160u * 1024u;
+}
+
+// ogs_spf_routes_whatif through the repair; call when whatif_repair_fits().
+hipError_t launch_whatif_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                const uint32_t* key, const ogs_unit* units, int n,
+                                uint32_t flags, const ogs_spf_out& out,
+                                const ogs_whatif_mods& mods, ogs_route_diff* diff,
+                                void* scratch, hipStream_t stream) {
+  const bool nodes = mods.node_off != nullptr;
+  const uint32_t lds = whatif_lds_bytes(g, nodes, mods.max_metric_per_unit);
+  hipError_t e = hipSuccess;
+  const bool changedOnly = (flags & OGS_F_CHANGED_ONLY) != 0;
+  auto k = changedOnly ? (nodes ? spf_whatif_repair_kernel<true, true>
+                                : spf_whatif_repair_kernel<true, false>)
+                       : (nodes ? spf_whatif_repair_kernel<false, true>
+                                : spf_whatif_repair_kernel<false, false>);
+  uint32_t* desc = repair_desc_rows(g, units, flags, diff, scratch, stream, &e);
   if (e != hipSuccess) return e;
   return launch_dyn_lds(k, dim3(n), dim3(kBlock), lds, stream, g, pt, key, units,
                         flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
@@ -1810,11 +1738,18 @@ bool scenario_frontier_fits(const ogs_graph& g, uint32_t flags, int W) {
       160u * 1024u;
 }
 
-template <int W>
+bool whatif_frontier_fits(const ogs_graph& g, uint32_t flags, int W, uint32_t maxMetric) {
+  return frontier_fits(g, flags, W) && maxMetric <= (1u << 14) &&
+      frontier_lds_bytes(uint32_t(g.max_nodes), W) + whatif_extra_bytes(g, maxMetric) +
+          kWhatifStaticLds <=
+      160u * 1024u;
+}
+
+template <int W, typename Mods>
 hipError_t launch_lists_w(const ogs_graph& g, const ogs_prefix_table& pt, const uint32_t* key,
                           const uint64_t* chunks, const uint32_t* nChunk,
                           const ogs_unit* units, int n, uint32_t flags, const ogs_spf_out& out,
-                          const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                          const Mods& mods, const ogs_route_diff* diff,
                           hipStream_t stream) {
   uint32_t* dist = static_cast<uint32_t*>(out.dist);
   const ogs_route_diff d = diff ? *diff : ogs_route_diff{};
@@ -1822,10 +1757,12 @@ hipError_t launch_lists_w(const ogs_graph& g, const ogs_prefix_table& pt, const 
   return launch_frontier<W, true, true, false>(g, pt, key, chunks, nChunk, units, n, flags, dist, out.nh, out, stream, mods, d);
 }
 
-hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
+namespace {
+template <typename Mods>
+hipError_t launch_lists(const ogs_graph& g, const ogs_prefix_table& pt,
                                  const uint32_t* key, const ogs_unit* units, int n,
                                  uint32_t flags, int W, const ogs_spf_out& out,
-                                 const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                                 const Mods& mods, const ogs_route_diff* diff,
                                  void* scratch, hipStream_t stream) {
   uint64_t* chunks = nullptr;
   uint32_t* nChunk = nullptr;
@@ -1837,6 +1774,24 @@ hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
     case 4: return launch_lists_w<4>(g, pt, key, chunks, nChunk, units, n, flags, out, mods, diff, stream);
     default: return hipErrorInvalidValue;
   }
+}
+}  // namespace
+
+hipError_t launch_frontier_lists(const ogs_graph& g, const ogs_prefix_table& pt,
+                                 const uint32_t* key, const ogs_unit* units, int n,
+                                 uint32_t flags, int W, const ogs_spf_out& out,
+                                 const ogs_scenario_mods& mods, const ogs_route_diff* diff,
+                                 void* scratch, hipStream_t stream) {
+  return launch_lists(g, pt, key, units, n, flags, W, out, mods, diff, scratch, stream);
+}
+
+// The full recompute over what-if lists (no node bits)
+hipError_t launch_frontier_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
+                                  const uint32_t* key, const ogs_unit* units, int n,
+                                  uint32_t flags, int W, const ogs_spf_out& out,
+                                  const ogs_whatif_mods& mods, const ogs_route_diff* diff,
+                                  void* scratch, hipStream_t stream) {
+  return launch_lists(g, pt, key, units, n, flags, W, out, mods, diff, scratch, stream);
 }
 
 }  // namespace ogs

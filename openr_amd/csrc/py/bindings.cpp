@@ -2174,9 +2174,23 @@ PYBIND11_MODULE(_decision, m) {
         py::arg("dualPermille") = 500);
   // What-if sweep over Python-built LinkState / PrefixState objects (kept
   // alive by the sweep). A scenario is {"links": [(node, ifName), ...],
-  // "nodesDown": [...], "nodesDrained": [...]}, every key optional.
+  // "nodesDown": [...], "nodesDrained": [...], "linkMetrics": [(node, ifName,
+  // metric), ...], "nodesSoftDrained": [(node, increment), ...]}, every key
+  // optional.
   auto toScenario = [](const py::dict& d) {
     LinkFailureSweep::Scenario s;
+    if (d.contains("linkMetrics")) {
+      for (const auto& [node, ifName, metric] :
+           d["linkMetrics"].cast<std::vector<std::tuple<std::string, std::string, int64_t>>>()) {
+        s.linkMetrics.push_back({node, ifName, metric});
+      }
+    }
+    if (d.contains("nodesSoftDrained")) {
+      for (const auto& [node, inc] :
+           d["nodesSoftDrained"].cast<std::vector<std::pair<std::string, int64_t>>>()) {
+        s.nodesSoftDrained.push_back({node, inc});
+      }
+    }
     if (d.contains("links")) {
       for (const auto& l : d["links"].cast<std::vector<std::pair<std::string, std::string>>>()) {
         s.linksDown.push_back({l.first, l.second});
@@ -2206,6 +2220,45 @@ PYBIND11_MODULE(_decision, m) {
           std::vector<std::string> drained;
           for (uint32_t v : x.drainedNodes) drained.push_back(f.names[v]);
           return py::make_tuple(dead, drained);
+        },
+        py::arg("linkState"), py::arg("me"), py::arg("scenario"));
+  // every list of the expansion: {"dead": [(node, other, ifName)], "drained":
+  // [node], "metrics": [(node, other, ifName, weight)] in edge-id order,
+  // "metricEdges": [edge id], "flags": [(node, bits)]}
+  m.def("expand_whatif",
+        [toScenario](const LinkState& ls, const std::string& me, const py::dict& sc) {
+          const auto x = LinkFailureSweep::expandScenario(ls, me, toScenario(sc));
+          const FlatTopology& f = ls.flat();
+          std::vector<uint32_t> src(f.edges.size());
+          for (uint32_t u = 0; u + 1 < f.rowPtr.size(); ++u) {
+            for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) src[e] = u;
+          }
+          auto edge = [&](uint32_t e) {
+            const std::string& n = f.names[src[e]];
+            return std::make_tuple(n, f.edgeLink[e]->getOtherNodeName(n),
+                                   f.edgeLink[e]->getIfaceFromNode(n));
+          };
+          std::vector<std::tuple<std::string, std::string, std::string>> dead;
+          for (uint32_t e : x.deadEdges) dead.push_back(edge(e));
+          std::sort(dead.begin(), dead.end());
+          std::vector<std::string> drained;
+          for (uint32_t v : x.drainedNodes) drained.push_back(f.names[v]);
+          std::vector<std::tuple<std::string, std::string, std::string, uint64_t>> metrics;
+          for (size_t i = 0; i < x.metricEdges.size(); ++i) {
+            metrics.push_back(std::tuple_cat(edge(x.metricEdges[i]),
+                                             std::make_tuple(x.metricVals[i])));
+          }
+          std::vector<std::pair<std::string, int>> flags;
+          for (size_t i = 0; i < x.flagNodes.size(); ++i) {
+            flags.emplace_back(f.names[x.flagNodes[i]], int(x.flagBits[i]));
+          }
+          py::dict out;
+          out["dead"] = dead;
+          out["drained"] = drained;
+          out["metrics"] = metrics;
+          out["metricEdges"] = x.metricEdges;
+          out["flags"] = flags;
+          return out;
         },
         py::arg("linkState"), py::arg("me"), py::arg("scenario"));
   py::class_<LinkFailureSweep>(m, "LinkFailureSweep")

@@ -5,7 +5,12 @@
   (c) 2,000 seeded link groups of 16 links,
   (d) the C4 link-failure variants (bench.py's 10,000, the same generator
       and seed) through the register form and, in the same process and
-      interleaved, forced through the bitset form.
+      interleaved, forced through the bitset form,
+  (e) every link cost out to 8x its weight, one scenario per link,
+  (f) every other node soft-drained by 1000,
+  (g) every link set to weight 1 (a lowered metric: the repair recomputes the
+      unit from the source inside the kernel), and the same set in mode kFull
+      (the full frontier form) beside it.
 Per set: launch + fetchUpdates ms (median of 5 after 2 warm-ups), the
 materialisation of every DecisionRouteUpdate, the total changed routes and the
 form taken. The CPU baseline is the oracle's own loop -- mutate its LinkState,
@@ -13,7 +18,7 @@ buildRouteDb, calculateUpdate, restore -- on one thread over a 64-scenario
 stratified sample of each set, EXTRAPOLATED to the set's size; the sample's
 updates, counts and updated RouteDbs must equal the sweep's.
 
-  python tools/whatif_sweep.py [--nodes 2000] [--sample 64]"""
+  python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg]"""
 import argparse
 import hashlib
 import json
@@ -34,11 +39,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=0, help="override C4's node count (smoke runs)")
     ap.add_argument("--sample", type=int, default=64)
+    ap.add_argument("--sets", default="abcdefg", help="the sets to run, by letter")
     args = ap.parse_args()
     import torch  # noqa: F401  (one HIP runtime: torch's)
     import _refcpu as O
     import openr_amd
     import whatif as W
+    import whatif_metric as WM
     from openr_amd.workloads import (C4_DUAL_PERMILLE, C4_OPTS, C4_SEED, C4_SOURCE,
                                      C4_VARIANTS)
     openr_amd.require_gpu()
@@ -47,30 +54,47 @@ def main():
     if args.nodes:
         opts["nodes"] = args.nodes
     me = C4_SOURCE
-    w = W.generated_world(M, "wan", opts)
+    w = WM.as_metric_world(W.generated_world(M, "wan", opts))
     names = sorted(n for n in w.adjdbs if n != me)
     links = sorted({min((n, a["ifName"]), (a["otherNodeName"], a["otherIfName"]))
                     for n, d in w.adjdbs.items() for a in d["adjacencies"]})
     rng = random.Random(0xC4F)
+
+    def both(n, ifn, metric):  # the link behind (n, ifn): both directions sent with `metric`
+        a = next(a for a in w.adjdbs[n]["adjacencies"] if a["ifName"] == ifn)
+        weight = max(a["metric"], next(b["metric"] for b in w.adjdbs[a["otherNodeName"]]["adjacencies"]
+                                       if b["ifName"] == a["otherIfName"]))
+        m = metric(weight)
+        return [(n, ifn, m), (a["otherNodeName"], a["otherIfName"], m)]
+
+    # (label, scenarios, register / bitset A/B, modes: 2 kChangedOnly, 0 kFull)
     sets = [
-        ("a: node down", [{"nodesDown": [n]} for n in names], False),
-        ("b: node drained", [{"nodesDrained": [n]} for n in names], False),
-        ("c: 16-link groups", [{"links": rng.sample(links, 16)} for _ in range(2000)], False),
+        ("a: node down", [{"nodesDown": [n]} for n in names], False, (2,)),
+        ("b: node drained", [{"nodesDrained": [n]} for n in names], False, (2,)),
+        ("c: 16-link groups", [{"links": rng.sample(links, 16)} for _ in range(2000)], False,
+         (2,)),
         ("d: C4 variants", [{"links": v} for v in M.link_failure_variants(
-            "wan", opts, C4_VARIANTS, C4_SEED, C4_DUAL_PERMILLE)], True),
+            "wan", opts, C4_VARIANTS, C4_SEED, C4_DUAL_PERMILLE)], True, (2,)),
+        ("e: link cost-out x8", [{"linkMetrics": both(n, i, lambda x: 8 * x)} for n, i in links],
+         False, (2,)),
+        ("f: node soft-drained", [{"nodesSoftDrained": [(n, 1000)]} for n in names], False, (2,)),
+        ("g: link set to 1", [{"linkMetrics": both(n, i, lambda x: 1)} for n, i in links], False,
+         (2, 0)),
     ]
+    sets = [s for s in sets if s[0][0] in args.sets]
     print(f"what-if sweep, C4 WAN: {len(w.adjdbs)} nodes, {w.directed_edges()} directed edges, "
-          f"source {me}, mode kChangedOnly")
+          f"source {me}, mode kChangedOnly unless a row says kFull")
     als, ls, ps = w.load(M, me)
     oracle = W.Oracle(O, w, me)
     out = []
-    for label, scs, ab in sets:
-        sweeps = []
-        for force in ((False, True) if ab else (False,)):
+    for label, scs, ab, modes in sets:
+        sweeps, names = [], []  # one sweep and its row label per (mode, list form)
+        for force, mode in [(f, m) for m in modes for f in ((False, True) if ab else (False,))]:
             sw = M.LinkFailureSweep(me, ls, ps, scs, True, False)
-            sw.setMode(2)
+            sw.setMode(mode)
             sw.setListForm(force)
             sweeps.append(sw)
+            names.append(label if mode == 2 else label + " (kFull)")
         # interleaved: one timed series per sweep, alternating
         ms = [[] for _ in sweeps]
         for i in range(7):
@@ -91,12 +115,12 @@ def main():
         for k, sw in enumerate(sweeps):
             W.check_sweep(sw, answers, label, idx)  # raises on any difference
             n, mat_ms = sw.materializeAll(0)
-            row = dict(set=label, scenarios=len(scs), form=FORMS[sw.form()],
+            row = dict(set=names[k], scenarios=len(scs), form=FORMS[sw.form()],
                        sweep_ms=median(ms[k][2:]), materialize_ms=mat_ms, changed_routes=n,
                        cpu_ms_per_scenario=cpu_ms, cpu_ms_extrapolated=cpu_ms * len(scs),
                        sample=len(idx), sample_digest=digest.hexdigest()[:16])
             out.append(row)
-            print(f"  {label:18s} {len(scs):6d} scenarios  {row['form']:15s} "
+            print(f"  {row['set']:26s} {len(scs):6d} scenarios  {row['form']:15s} "
                   f"launch+fetch {row['sweep_ms']:8.3f} ms  materialise {mat_ms:8.3f} ms  "
                   f"changed routes {n:9d}  | oracle loop {cpu_ms:7.3f} ms/scenario x "
                   f"{len(scs)} = {cpu_ms * len(scs) / 1e3:8.2f} s (extrapolated from "
