@@ -362,7 +362,9 @@ int ogs_host_free(void* hptr);
  *                 every ogs_spf_routes call takes that path (A/B, tests).
  *   "spf_global_sync": 1 (default) global-path rounds end with drained
  *                 stores + a barrier and state is read through L2-served
- *                 (sc1) loads; 0 agent-scope fences per round (A/B).
+ *                 (sc1) loads; 0 agent-scope fences per round (A/B). Not
+ *                 read by ogs_spf_routes_whatif_global, whose forms are all
+ *                 of the first kind ("spf_global_lds" applies there).
  *   "spf_global_lds": 1 (default) global-path distances and next-hop words
  *                 in LDS where both fit, else distances only; 2 distances
  *                 only; 3 distances and next-hop words in two phases, never
@@ -653,6 +655,56 @@ int ogs_spf_routes_whatif(const ogs_graph* graph,
                           const ogs_whatif_mods* mods,
                           ogs_route_diff* diff, uint32_t flags,
                           int32_t nh_words, ogs_spf_out* out, void* stream);
+
+/* ogs_spf_routes_whatif for areas of ANY size (max_nodes up to 2^21): every
+ * unit's SPF runs in the global-state kernels (one 1,024-thread workgroup per
+ * unit, state in LDS where it fits, else in HBM), always as a full recompute,
+ * with the unit's modifications applied while it relaxes; a second launch
+ * computes the unit's routes against its own node-flag row and diffs them
+ * against the base records. Same arguments, argument rules (same order, same
+ * statuses), mods rules (skipped ids, dead wins over overridden, lists ignored
+ * under OGS_F_HOP_METRIC, refused units), outputs, diff and
+ * ogs_route_changes_gather contract as ogs_spf_routes_whatif, except:
+ *   - nh_words must be 1, 2 or 4 and OGS_F_WIDE_METRIC is not taken:
+ *     OGS_E_UNSUPPORTED otherwise; node bits (OGS_NODE_OVERLOADED = a hard
+ *     drain) and metric lists run in every mode and at every width;
+ *   - graph->edge_src may be NULL;
+ *   - OGS_F_INCREMENTAL alone computes what the full form computes. With
+ *     OGS_F_INCREMENTAL | OGS_F_CHANGED_ONLY, diff->base_dist and
+ *     graph->edge_src, a unit with no node bits, no lowered metric and no dead
+ *     or raised edge that is tight in the base SPF (up, tail reached, tail the
+ *     source or not overloaded, base_dist[tail] + w == base_dist[head]) runs
+ *     nothing: nothing on a shortest path moved, so its counts are {0, 0} and
+ *     its `changed` row stays zero (out->dist / out->nh, when given, get the
+ *     base's rows). OGS_F_CHANGED_ONLY needs nh_words 1, as for the other
+ *     entries, so exits exist at one next-hop word only. Without edge_src no
+ *     unit takes that exit; the results are the same.
+ * Workspace, proportional to n_units; per unit, with S_n = max_nodes:
+ *   12 * S_n                        frontier lists and stamps
+ *   + 8 * ceil(max_edges / 32)      dead and overridden edge bitsets
+ *   + 4                             unit status
+ *   + S_n rounded up to 4           the unit's node-flag row, when node_off
+ *                                   is given
+ *   + 4 * S_n                       when out->dist is NULL
+ *   + 4 * nh_words * S_n            when out->nh is NULL
+ * (each region of the call rounded up to 256 bytes). A caller bounds the
+ * workspace by calling over chunks of units: units, out and diff rows advance
+ * per chunk, dead_off / node_off / metric_off are absolute offsets, so the
+ * pointer to a chunk's first offset serves as it is. */
+int ogs_spf_routes_whatif_global(const ogs_graph* graph,
+                                 const ogs_prefix_table* prefixes,
+                                 const ogs_unit* units /* device */, int32_t n_units,
+                                 const ogs_whatif_mods* mods,
+                                 ogs_route_diff* diff, uint32_t flags,
+                                 int32_t nh_words, ogs_spf_out* out, void* stream);
+
+/* Host only, no device needed: 1 when the LDS forms behind
+ * ogs_spf_routes_variants / _scenarios / _whatif cannot hold an area of
+ * graph->max_nodes nodes at this width (they return OGS_E_UNSUPPORTED) and
+ * ogs_spf_routes_whatif_global takes it (32-bit distances, nh_words 1, 2 or
+ * 4, max_nodes in (0, 2^21]); else 0. Reads graph->max_nodes and
+ * graph->max_degree only. */
+int ogs_whatif_needs_global(const ogs_graph* graph, uint32_t flags, int32_t nh_words);
 
 /* Compact list of the changed routes of n_units variants (SURVEY.md §8(f)
  * f1): what DecisionRouteDb::calculateUpdate (SpfSolver.cpp:21-56) hands

@@ -36,6 +36,7 @@ EXPORTS = [
     "ogs_route_delta",
     "ogs_spf_routes_scenarios", "ogs_ctx_spf_routes_scenarios",
     "ogs_spf_routes_whatif", "ogs_ctx_spf_routes_whatif",
+    "ogs_spf_routes_whatif_global", "ogs_whatif_needs_global",
 ]
 
 OGS_WHATIF_REFUSED = 0xFFFFFFFF
@@ -175,6 +176,11 @@ def load(path=None):
             f = getattr(lib, fn)
             f.argtypes = a
             f.restype = ctypes.c_int
+    # the global-state what-if form (no ogs_ctx_ twin)
+    lib.ogs_spf_routes_whatif_global.argtypes = plain["ogs_spf_routes_whatif"]
+    lib.ogs_spf_routes_whatif_global.restype = ctypes.c_int
+    lib.ogs_whatif_needs_global.argtypes = [ctypes.POINTER(Graph), U32, I32]
+    lib.ogs_whatif_needs_global.restype = ctypes.c_int
     return lib
 
 

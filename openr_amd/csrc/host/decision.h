@@ -1194,7 +1194,10 @@ DecisionRouteDb materializeRouteDb(
 // when a scenario moves a metric or soft-drains a node; route diff fused in;
 // form()); only the
 // changed records are gathered on the device (ogs_route_changes_gather) and
-// materialised. Areas with zero / negative link metrics or path sums past 32
+// materialised. Areas past the LDS forms' node limit run every scenario kind
+// through ogs_spf_routes_whatif_global (kGlobalState: one workgroup per
+// scenario on the global-state SPF, in chunks of scenarios), with the same
+// device diff and gather. Areas with zero / negative link metrics or path sums past 32
 // bits, and sources of degree > 128, run each variant as its own topology
 // (exact extraction order, 64-bit distances), in ogs_spf_routes launches of
 // up to kExactChunk (256) topologies each, rebuilt from the live `ls` / `ps`
@@ -1281,10 +1284,22 @@ class LinkFailureSweep {
   // 0, a negative one, or one past the 32-bit path-sum guard). Before the
   // first launch: the form the scenarios alone select. setMode / setListForm
   // select again and drop fetched results.
-  enum Form { kRegisterList = 0, kEdgeBitset = 1, kTopologyCopies = 2 };
+  // kGlobalState: areas past the LDS forms' node limit
+  // (ogs_whatif_needs_global: 16,385+ nodes at one next-hop word) outside the
+  // exact domain. Every scenario kind goes through ogs_whatif_mods to
+  // ogs_spf_routes_whatif_global: one workgroup per scenario on the
+  // global-state SPF, always a full recompute, the route diff on the device;
+  // launched over chunks of scenarios so that the workspace stays bounded.
+  enum Form { kRegisterList = 0, kEdgeBitset = 1, kTopologyCopies = 2, kGlobalState = 3 };
   Form form() const { return form_; }
   // A/B and tests only: every list through the bitset form
   void setListForm(bool forceBitset);
+  // A/B and tests only: the global-state form on an area the LDS forms hold
+  // (not in the exact domain). Selects again and drops fetched results.
+  void setGlobalForm(bool forceGlobal);
+  // scenarios per ogs_spf_routes_whatif_global call; 0 (default): the most
+  // whose workspace stays within 1 GiB. Drops fetched results.
+  void setGlobalChunk(size_t n);
   // base RouteDb records (the diff's reference); launch() runs it when needed
   void runBase(void* stream = nullptr);
   // every variant + diff, one launch; records = false keeps only the diff
@@ -1359,6 +1374,13 @@ class LinkFailureSweep {
   bool whatif_{false};
   DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_, dFlagOff_, dFlagNode_, dFlagBits_;
   bool forceBitset_{false};
+  bool forceGlobal_{false}, needsGlobal_{false};
+  size_t globalChunk_{0};
+  void uploadWhatifLists();  // the metric and flag lists (once)
+  bool whatifUploaded_{false};
+  size_t globalChunkUnits(bool ownRows) const;
+  void globalLaunch(const ogs_graph& g, const ogs_prefix_table& pt, const ogs_route_diff& diff,
+                    uint32_t fl, const ogs_spf_out& out, void* stream);
   Form form_{kRegisterList};
   int deadPer_{0};  // dDead_'s dead_per_unit (0: not built yet)
   HostBatchImage img_;  // device copy of hb_

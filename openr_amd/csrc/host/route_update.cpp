@@ -207,6 +207,7 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
 
 LinkFailureSweep::Form LinkFailureSweep::selectForm() const {
   if (exact_) return kTopologyCopies;
+  if (needsGlobal_ || forceGlobal_) return kGlobalState;
   if (maxDead_ <= kRegisterMax && drainList_.empty() && !forceBitset_ && !whatif_) {
     return kRegisterList;
   }
@@ -241,6 +242,92 @@ void LinkFailureSweep::reselect() {
 void LinkFailureSweep::setListForm(bool forceBitset) {
   forceBitset_ = forceBitset;
   reselect();
+}
+
+void LinkFailureSweep::setGlobalForm(bool forceGlobal) {
+  forceGlobal_ = forceGlobal;
+  reselect();
+  if (form_ == kGlobalState) uploadWhatifLists();
+}
+
+void LinkFailureSweep::setGlobalChunk(size_t n) {
+  globalChunk_ = n;
+  reselect();
+}
+
+// The metric and flag lists of ogs_whatif_mods (the dead lists are always
+// there): for the what-if entry when a scenario moves a metric or sets a
+// soft-drain bit, for the global form whenever it is selected.
+void LinkFailureSweep::uploadWhatifLists() {
+  if (whatifUploaded_ || exact_) return;
+  whatifUploaded_ = true;
+  std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());  // all within 32 bits
+  dMetricOff_.upload(metricOff_.data(), metricOff_.size());
+  dMetricEdge_.upload(metricEdge_.data(), metricEdge_.size());
+  dMetricVal_.upload(vals.data(), vals.size());
+  if (!flagNode_.empty()) {
+    dFlagOff_.upload(flagOff_.data(), flagOff_.size());
+    dFlagNode_.upload(flagNode_.data(), flagNode_.size());
+    dFlagBits_.upload(flagBits_.data(), flagBits_.size());
+  }
+}
+
+// Scenarios per ogs_spf_routes_whatif_global call: the most whose workspace
+// (openr_gpu.h: the per-unit bytes, each of the call's six regions rounded up
+// to 256) stays within 1 GiB. ownRows: the launch passes dist / next-hop
+// rows of its own, so the workspace holds none.
+size_t LinkFailureSweep::globalChunkUnits(bool ownRows) const {
+  if (globalChunk_) return globalChunk_;
+  const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
+  const size_t E = size_t(std::max(hb_.maxEdges, 0));
+  const size_t rows = ownRows ? 0 : 4 * Sn + 4 * size_t(W_) * Sn;
+  const size_t flagRow = flagNode_.empty() ? 0 : ((Sn + 3) & ~size_t(3));
+  const size_t perUnit = 12 * Sn + 8 * ((E + 31) / 32) + 4 + flagRow + rows;
+  constexpr size_t kBudget = (size_t(1) << 30) - 6 * 255;  // the regions' padding
+  return std::max<size_t>(1, kBudget / perUnit);
+}
+
+// ogs_spf_routes_whatif_global over chunks of scenarios: unit, record and
+// diff rows advance per chunk; the lists' offsets are absolute, so each
+// chunk's slice of an offset array serves as it is.
+void LinkFailureSweep::globalLaunch(const ogs_graph& g, const ogs_prefix_table& pt,
+                                    const ogs_route_diff& diff, uint32_t fl,
+                                    const ogs_spf_out& out, void* stream) {
+  uploadWhatifLists();
+  const size_t U = numVariants(), Sn = size_t(std::max(hb_.maxNodes, 1));
+  const size_t chunk = globalChunkUnits(out.dist && out.nh);
+  const bool nodes = !flagNode_.empty(), metrics = !metricEdge_.empty();
+  for (size_t c0 = 0; c0 < U; c0 += chunk) {
+    const size_t n = std::min(chunk, U - c0);
+    ogs_whatif_mods mods{dDeadOff_.as<uint32_t>() + c0, dDeadList_.as<uint32_t>(),
+                         nodes ? dFlagOff_.as<uint32_t>() + c0 : nullptr,
+                         nodes ? dFlagNode_.as<uint32_t>() : nullptr,
+                         nodes ? dFlagBits_.as<uint8_t>() : nullptr,
+                         metrics ? dMetricOff_.as<uint32_t>() + c0 : nullptr,
+                         metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
+                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, maxMetricList_};
+    ogs_route_diff d = diff;
+    d.changed += c0 * words_;
+    d.counts += c0 * 2;
+    d.base_desc = nullptr;
+    ogs_spf_out o = out;
+    auto adv = [&](auto*& p, size_t stride) {
+      if (p) p += c0 * stride;
+    };
+    uint32_t* dist = static_cast<uint32_t*>(o.dist);
+    uint32_t* metric = static_cast<uint32_t*>(o.metric);
+    adv(dist, Sn);
+    adv(metric, Sp_);
+    o.dist = dist;
+    o.metric = metric;
+    adv(o.nh, size_t(W_) * Sn);
+    adv(o.meta, Sp_);
+    adv(o.sel, Sp_);
+    adv(o.mask, size_t(W_) * Sp_);
+    ogsCheck(ogs_spf_routes_whatif_global(&g, &pt, dUnits_.as<ogs_unit>() + c0, int32_t(n), &mods,
+                                          &d, fl, W_, &o, stream),
+             "ogs_spf_routes_whatif_global");
+  }
 }
 
 LinkFailureSweep::LinkFailureSweep(
@@ -302,6 +389,12 @@ LinkFailureSweep::LinkFailureSweep(
       if (n != 0 && w > 0x7FFFFFFEull / n) exact_ = true;
     }
   }
+  if (!exact_) {
+    ogs_graph shape{};  // the two fields the question reads
+    shape.max_nodes = hb_.maxNodes;
+    shape.max_degree = hb_.maxDegree;
+    needsGlobal_ = ogs_whatif_needs_global(&shape, 0u, W_) != 0;
+  }
   form_ = selectForm();
 
   const size_t U = scenarios.size(), Sn = size_t(std::max(hb_.maxNodes, 1));
@@ -320,17 +413,7 @@ LinkFailureSweep::LinkFailureSweep(
     dDrainOff_.upload(drainOff_.data(), drainOff_.size());
     dDrainList_.upload(drainList_.data(), drainList_.size());
   }
-  if (whatif_ && !exact_) {
-    std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());  // all within 32 bits
-    dMetricOff_.upload(metricOff_.data(), metricOff_.size());
-    dMetricEdge_.upload(metricEdge_.data(), metricEdge_.size());
-    dMetricVal_.upload(vals.data(), vals.size());
-    if (!flagNode_.empty()) {
-      dFlagOff_.upload(flagOff_.data(), flagOff_.size());
-      dFlagNode_.upload(flagNode_.data(), flagNode_.size());
-      dFlagBits_.upload(flagBits_.data(), flagBits_.size());
-    }
-  }
+  if ((whatif_ || form_ == kGlobalState) && !exact_) uploadWhatifLists();
   {
     const std::vector<uint32_t> cls = advClasses(table_);
     dAdvClass_.upload(cls.data(), cls.size());
@@ -501,7 +584,9 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   uint32_t fl = flags();
   if (mode_ != kFull) fl |= OGS_F_INCREMENTAL;
   if (changedOnly) fl |= OGS_F_CHANGED_ONLY;
-  if (form_ == kRegisterList) {
+  if (form_ == kGlobalState) {
+    globalLaunch(g, pt, diff, fl, out, stream);
+  } else if (form_ == kRegisterList) {
     // the lists as ogs_unit_mods slots: 4 a unit (two links, both directions)
     // as every sweep before scenarios had them, up to 8 when a list is longer
     if (!deadPer_) uploadRegisterSlots();

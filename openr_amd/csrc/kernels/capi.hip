@@ -482,13 +482,16 @@ int ogs_spf_routes_scenarios(const ogs_graph* graph,
   return e == hipSuccess ? OGS_OK : hipFail(e, "scenario launch");
 }
 
-int ogs_spf_routes_whatif(const ogs_graph* graph,
-                          const ogs_prefix_table* prefixes,
-                          const ogs_unit* units, int32_t n_units,
-                          const ogs_whatif_mods* mods,
-                          ogs_route_diff* diff, uint32_t flags,
-                          int32_t nh_words, ogs_spf_out* out, void* stream) {
-  // the rules shared with ogs_spf_routes_scenarios, in its order
+// The argument rules of the two what-if entries (ogs_spf_routes_whatif,
+// ogs_spf_routes_whatif_global), stated once: the rules shared with
+// ogs_spf_routes_scenarios, in its order. *done: the call is finished with the
+// returned status (an error, or n_units == 0).
+static int check_whatif_args(const ogs_graph* graph, const ogs_prefix_table* prefixes,
+                             const ogs_unit* units, int32_t n_units,
+                             const ogs_whatif_mods* mods, const ogs_route_diff* diff,
+                             uint32_t flags, int32_t nh_words, const ogs_spf_out* out,
+                             bool* done) {
+  *done = true;
   if (!graph || !prefixes || !out) return fail(OGS_E_INVALID, "graph/prefixes/out is NULL");
   if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
   if (n_units == 0) return OGS_OK;
@@ -519,6 +522,20 @@ int ogs_spf_routes_whatif(const ogs_graph* graph,
   if (nh_words < 1) {
     return fail(OGS_E_INVALID, "nh_words < 1");
   }
+  *done = false;
+  return OGS_OK;
+}
+
+int ogs_spf_routes_whatif(const ogs_graph* graph,
+                          const ogs_prefix_table* prefixes,
+                          const ogs_unit* units, int32_t n_units,
+                          const ogs_whatif_mods* mods,
+                          ogs_route_diff* diff, uint32_t flags,
+                          int32_t nh_words, ogs_spf_out* out, void* stream) {
+  bool done = false;
+  const int rc0 = check_whatif_args(graph, prefixes, units, n_units, mods, diff, flags, nh_words,
+                                    out, &done);
+  if (done) return rc0;
   int unsupported = 0;
   hipError_t e = ogs::launch_whatif(*graph, *prefixes, units, n_units, *mods, diff, flags,
                                     nh_words, *out, static_cast<hipStream_t>(stream),
@@ -538,6 +555,30 @@ int ogs_spf_routes_whatif(const ogs_graph* graph,
                 "the edge bitsets and the metric slice do not fit the LDS of any form");
   }
   return e == hipSuccess ? OGS_OK : hipFail(e, "what-if launch");
+}
+
+int ogs_spf_routes_whatif_global(const ogs_graph* graph,
+                                 const ogs_prefix_table* prefixes,
+                                 const ogs_unit* units, int32_t n_units,
+                                 const ogs_whatif_mods* mods,
+                                 ogs_route_diff* diff, uint32_t flags,
+                                 int32_t nh_words, ogs_spf_out* out, void* stream) {
+  bool done = false;
+  const int rc0 = check_whatif_args(graph, prefixes, units, n_units, mods, diff, flags, nh_words,
+                                    out, &done);
+  if (done) return rc0;
+  if (!ogs::whatif_global_takes(*graph, flags, nh_words)) {
+    return fail(OGS_E_UNSUPPORTED,
+                "the global what-if form takes 32-bit distances and nh_words 1, 2 or 4");
+  }
+  hipError_t e = ogs::launch_whatif_global(*graph, *prefixes, units, n_units, *mods, diff, flags,
+                                           nh_words, *out, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? OGS_OK : hipFail(e, "global what-if launch");
+}
+
+int ogs_whatif_needs_global(const ogs_graph* graph, uint32_t flags, int32_t nh_words) {
+  if (!graph || !ogs::whatif_global_takes(*graph, flags, nh_words)) return 0;
+  return ogs::frontier_fits(*graph, flags, nh_words) ? 0 : 1;
 }
 
 int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,

@@ -94,6 +94,13 @@ hipError_t launch_routes_from_spf(const ogs_graph& g, const ogs_prefix_table& pt
                                   const ogs_unit* units, int n, const void* dist,
                                   const uint32_t* nh, const uint32_t* reach, uint32_t flags,
                                   int W, const ogs_spf_out& out, hipStream_t stream);
+// ogs_spf_routes_whatif_global: what-if lists over the global-state SPF (any
+// size; call when whatif_global_takes()), route diff in a second launch
+bool whatif_global_takes(const ogs_graph& g, uint32_t flags, int W);
+hipError_t launch_whatif_global(const ogs_graph& g, const ogs_prefix_table& pt,
+                                const ogs_unit* units, int nUnits, const ogs_whatif_mods& mods,
+                                const ogs_route_diff* diff, uint32_t flags, int W,
+                                const ogs_spf_out& out, hipStream_t stream);
 // ksp.hip
 hipError_t launch_ksp(const ogs_graph& g, const ogs_path_unit* units,
                       int nUnits, const uint32_t* masks, uint32_t maskWords,

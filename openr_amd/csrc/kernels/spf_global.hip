@@ -34,8 +34,17 @@
 //
 // Routes: route_global.h, one thread per (unit, prefix) against the unit's
 // state in HBM. u32 or u64 distances (OGS_F_WIDE_METRIC).
+//
+// What-if units (ogs_spf_routes_whatif_global): both kernels take a mods
+// policy. WhatifRows keeps the unit's dead / overridden edge bitsets and its
+// node-flag row in per-unit HBM rows of the workspace (the LDS forms have no
+// room left at 20k nodes), fills them before round 1 and reads them with sc1
+// loads beside the edge loads; NoMods is the plain build, compiled to the
+// code these kernels had before the policy. Routes and the diff against the
+// base records: route_global_diff_kernel (route_global.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "openr_gpu.h"
@@ -83,20 +92,198 @@ struct GUnit {
 
 // kB edges of a row from edge e on (`left` remain), decoded: target, whether
 // the link is up, and the candidate distance dv + w
+// (mu: the unit's mods policy, below -- a dead edge reads as down, an
+// overridden one carries the unit's weight; the step's one or two bitset
+// words are loaded beside its edge words)
 template <typename D, int kB>
 struct GEdges {
   uint32_t t[kB];
   D c[kB];
   bool up[kB];
-  __device__ __forceinline__ GEdges(const GUnit<D>& u, D dv, uint32_t e, uint32_t left) {
+  template <class MU>
+  __device__ __forceinline__ GEdges(const GUnit<D>& u, const MU& mu, D dv, uint32_t e,
+                                    uint32_t left) {
+    uint64_t x[kB];
 #pragma unroll
     for (int k = 0; k < kB; ++k) {
-      const uint64_t x = uint32_t(k) < left ? u.edges[e + k] : uint64_t(OGS_EDGE_DOWN);
-      const uint32_t lo = static_cast<uint32_t>(x);
-      up[k] = !(lo & OGS_EDGE_DOWN);
-      t[k] = edge_dst(lo);
-      c[k] = dv + u.weight(x);
+      x[k] = uint32_t(k) < left ? u.edges[e + k] : uint64_t(OGS_EDGE_DOWN);
     }
+    if constexpr (MU::kOn) {
+      const uint32_t last = e + (left < uint32_t(kB) ? left : uint32_t(kB)) - 1u;  // left >= 1
+      const uint64_t b0 = mu.word(e >> 5), b1 = mu.word(last >> 5);
+#pragma unroll
+      for (int k = 0; k < kB; ++k) {
+        const uint32_t lo = static_cast<uint32_t>(x[k]);
+        const uint64_t bw = ((e + k) >> 5) == (e >> 5) ? b0 : b1;
+        const uint32_t bit = 1u << ((e + k) & 31u);
+        const bool live = uint32_t(k) < left;  // past the row: no bit is this edge's
+        up[k] = !(lo & OGS_EDGE_DOWN) && !(live && (static_cast<uint32_t>(bw) & bit));
+        t[k] = edge_dst(lo);
+        c[k] = dv + ((live && (static_cast<uint32_t>(bw >> 32) & bit)) ? D(mu.search(e + k))
+                                                                      : u.weight(x[k]));
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kB; ++k) {
+        const uint32_t lo = static_cast<uint32_t>(x[k]);
+        up[k] = !(lo & OGS_EDGE_DOWN);
+        t[k] = edge_dst(lo);
+        c[k] = dv + u.weight(x[k]);
+      }
+    }
+  }
+};
+
+// ---- the unit's modifications (ogs_spf_routes_whatif_global) ----------------
+// A mods policy answers, shaped like WhatifBits of spf_frontier.hip: is
+// directed edge e dead in this unit, what is e's weight, is node v hard-
+// drained. NoMods is the plain build: the kernels compile to what they were
+// before the policy existed.
+struct NoMods {
+  static constexpr bool kOn = false;
+};
+
+// What the what-if launch hands every workgroup besides the plain arguments.
+struct GWhatifArgs {
+  ogs_whatif_mods mods;
+  const uint32_t* edgeSrc;   // graph->edge_src or nullptr (no exit-only units)
+  const uint32_t* baseDist;  // diff->base_dist when exit-only units are allowed, else nullptr
+  const uint32_t* baseNh;
+  uint32_t* exitDist;        // the caller's dist / nh rows (an exit-only unit copies the
+  uint32_t* exitNh;          // base's [S_n] rows there: set at W == 1 only) or nullptr
+  uint32_t* counts;          // diff->counts or nullptr
+  uint64_t* bits;            // [U][ew] {dead word, overridden word << 32}
+  uint8_t* frows;            // [U][SnB] the units' node-flag rows (nullptr: no node lists)
+  uint32_t* skip;            // [U] 1: the unit ran no SPF (refused / exit-only)
+  uint32_t ew, SnB;
+};
+
+// Per-unit HBM rows in the workspace, filled by the unit's workgroup before
+// round 1: at 20k nodes the LDS forms leave no room for an edge bitset. The
+// rows are written inside the launch, so the fill ends in round_sync<true>()
+// and every later read is an sc1 load (ld_state<true>), as for the SPF state.
+// An overridden edge finds its weight by binary search over the unit's
+// ascending (metric_edges, metric_vals) slice in global memory; the search
+// stays inside [0, n) whatever the slice holds.
+struct WhatifRows {
+  static constexpr bool kOn = true;
+  const uint64_t* bb;
+  const uint32_t* me;
+  const uint32_t* mv;
+  uint32_t n;
+  const uint8_t* nflags;  // the unit's row, or the topology's when it has no node bits
+
+  __device__ __forceinline__ uint64_t word(uint32_t i) const { return ld_state<true>(bb + i); }
+  __device__ __forceinline__ bool has(uint32_t e) const {
+    return (static_cast<uint32_t>(word(e >> 5)) >> (e & 31u)) & 1u;
+  }
+  __device__ __forceinline__ uint32_t search(uint32_t e) const {
+    uint32_t lo = 0, hi = n;  // n >= 1: a set bit came from the slice
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (me[mid] <= e) lo = mid; else hi = mid;
+    }
+    return mv[lo];
+  }
+  __device__ __forceinline__ uint32_t weight(uint32_t e, uint64_t x) const {
+    return ((static_cast<uint32_t>(word(e >> 5) >> 32) >> (e & 31u)) & 1u)
+        ? search(e) : static_cast<uint32_t>(x >> 32);
+  }
+  __device__ __forceinline__ bool drained(uint32_t v) const {
+    return ld_state<true>(nflags + v) & OGS_NODE_OVERLOADED;
+  }
+
+  // Fills the unit's rows; false when the unit runs no SPF: refused (a bad
+  // weight, a slice past max_metric_per_unit: counts = OGS_WHATIF_REFUSED) or
+  // exit-only (no node bits, no lowered metric, no dead or raised edge tight
+  // in the base: nothing on a shortest path moved, counts = {0, 0}). Both
+  // decisions are uniform across the workgroup.
+  __device__ __forceinline__ bool setup(const GWhatifArgs& a, const ogs_graph& g,
+                                        const GUnit<uint32_t>& u) {
+    constexpr uint32_t kInf = 0xFFFFFFFFu;
+    __shared__ uint32_t wf[2];  // refused, something on a base shortest path moved
+    const uint32_t tid = threadIdx.x, u0 = u.u0;
+    const ogs_whatif_mods& m = a.mods;
+    // (never past the row the launch sized from graph->max_edges)
+    const uint32_t E = min(u.gRow[u.N] - u.e0, a.ew * 32u);
+    const uint32_t words = (E + 31u) / 32u;
+    uint64_t* row = a.bits + size_t(u0) * a.ew;
+    uint32_t* row32 = reinterpret_cast<uint32_t*>(row);
+    const bool metrics = m.metric_off && !u.hop;  // ignored under OGS_F_HOP_METRIC
+    const uint32_t m0 = metrics ? m.metric_off[u0] : 0u;
+    uint32_t mn = metrics ? m.metric_off[u0 + 1] - m0 : 0u;
+    const bool tooLong = mn > m.max_metric_per_unit;
+    if (tooLong) mn = 0u;
+    const uint32_t r0 = m.node_off ? m.node_off[u0] : 0u;
+    const uint32_t r1 = m.node_off ? m.node_off[u0 + 1] : 0u;
+    const bool nodes = r1 > r0;
+    uint8_t* frow = nodes ? a.frows + size_t(u0) * a.SnB : nullptr;
+    const uint32_t* bD = a.baseDist;
+    const bool exits = bD && a.edgeSrc && !nodes;
+
+    for (uint32_t w = tid; w < words; w += kGBlock) row[w] = 0ull;
+    if (nodes) {
+      for (uint32_t v = tid; v < u.N; v += kGBlock) frow[v] = u.nflags[v];
+    }
+    if (tid == 0) {
+      wf[0] = tooLong ? 1u : 0u;
+      wf[1] = 0u;
+    }
+    round_sync<true>();
+    // is edge e (in range, weight w in the base) tight in the base?
+    auto tight = [&](uint32_t e, uint64_t x) {
+      const uint32_t lo = static_cast<uint32_t>(x);
+      if (lo & OGS_EDGE_DOWN) return false;
+      const uint32_t p = a.edgeSrc[u.e0 + e], v = edge_dst(lo);
+      const uint32_t dp = bD[p];
+      return (p == u.s || !(u.nflags[p] & OGS_NODE_OVERLOADED)) && dp != kInf &&
+          dp + u.weight(x) == bD[v];
+    };
+    for (uint32_t i = m.dead_off[u0] + tid; i < m.dead_off[u0 + 1]; i += kGBlock) {
+      const uint32_t e = m.dead_edges[i];
+      if (e >= E) continue;  // OGS_NODE_NONE or a bad id: never outside the row
+      atomicOr(&row32[2u * (e >> 5)], 1u << (e & 31u));
+      if (exits && tight(e, u.edges[e])) wf[1] = 1u;
+    }
+    for (uint32_t i = tid; i < mn; i += kGBlock) {
+      const uint32_t e = m.metric_edges[m0 + i], v = m.metric_vals[m0 + i];
+      if (e >= E) continue;  // skipped: sets no bit, so the search never returns it
+      if (v - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
+        wf[0] = 1u;
+        continue;
+      }
+      atomicOr(&row32[2u * (e >> 5) + 1u], 1u << (e & 31u));
+      if (!exits) continue;
+      const uint64_t x = u.edges[e];
+      if (static_cast<uint32_t>(x) & OGS_EDGE_DOWN) continue;
+      const uint32_t w = static_cast<uint32_t>(x >> 32);
+      if (v < w || (v > w && tight(e, x))) wf[1] = 1u;
+    }
+    for (uint32_t i = r0 + tid; i < r1; i += kGBlock) {
+      const uint32_t x = m.node_ids[i];
+      if (x < u.N) frow[x] = u.nflags[x] | m.node_bits[i];
+    }
+    round_sync<true>();
+    const bool refused = wf[0] != 0u;
+    const bool exit = !refused && exits && wf[1] == 0u;
+    if (tid == 0) a.skip[u0] = (refused || exit) ? 1u : 0u;
+    if (a.counts && tid < 2) a.counts[size_t(u0) * 2 + tid] = refused ? OGS_WHATIF_REFUSED : 0u;
+    // (exits only at W == 1: the unit's next-hop row is u0 * Sn, one word a node)
+    if (exit && a.exitDist) {
+      for (uint32_t v = tid; v < u.N; v += kGBlock) a.exitDist[size_t(u0) * u.Sn + v] = bD[v];
+    }
+    if (exit && a.exitNh) {
+      for (uint32_t v = tid; v < u.N; v += kGBlock) {
+        a.exitNh[size_t(u0) * u.Sn + v] = a.baseNh[v];
+      }
+    }
+    if (refused || exit) return false;
+    bb = row;
+    me = m.metric_edges + m0;
+    mv = m.metric_vals + m0;
+    n = mn;
+    nflags = nodes ? frow : u.nflags;
+    return true;
   }
 };
 
@@ -325,11 +512,15 @@ struct LdsBothState {
 // Wn: the next-hop word count where F::kW == kWRuntime (sources of more than
 // 512 links; rslot is never read: push-style relaxation, link slots from the
 // source's own row).
-template <class F>
+// M: the mods policy. MA: nothing for NoMods -- the plain kernels keep the
+// argument list they had --, GWhatifArgs for WhatifRows (a unit that is
+// refused or exit-only leaves before its state is touched).
+template <class F, class M = NoMods, class... MA>
 __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
     ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags, int Wn,
     typename F::Dist* __restrict__ oDist, uint32_t* __restrict__ oNh,
-    uint32_t* __restrict__ scratch) {
+    uint32_t* __restrict__ scratch, MA... ma) {
+  static_assert(sizeof...(MA) == (M::kOn ? 1 : 0), "the policy's arguments, or none");
   using D = typename F::Dist;
   constexpr int W = F::kW;
   constexpr int kUnrollW = W == kWRuntime ? 1 : W;  // a runtime count: no unrolling
@@ -338,6 +529,13 @@ __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
   __shared__ uint32_t qcnt[3];
   const uint32_t tid = threadIdx.x;
   const GUnit<D> u(g, units[blockIdx.x], flags);
+  M mu;
+  if constexpr (M::kOn) {
+    if (!mu.setup(ma..., g, u)) return;
+  }
+  auto drained = [&](uint32_t v) {
+    if constexpr (M::kOn) return mu.drained(v); else return u.drained(v);
+  };
   uint32_t* rows = scratch + u.u0 * 3 * u.Sn;
   F st(u, Wn, oDist, oNh, smem);
   auto mem = st.member(rows);
@@ -377,11 +575,11 @@ __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
 
   // ---- dist phase: rows of the nodes whose distance dropped last round ----
   const uint32_t r0 = rounds(1u, 1u, [&](uint32_t v, uint32_t r) {
-    if (v != u.s && u.drained(v)) return;  // 741-752
+    if (v != u.s && drained(v)) return;  // 741-752
     const D dv = st.ld_dist(v);
     const uint32_t b = u.gRow[v] - u.e0, m = u.gRow[v + 1] - u.e0 - b;
     for (uint32_t j0 = 0; j0 < m; j0 += kGRow) {
-      const GEdges<D, kGRow> e(u, dv, b + j0, m - j0);
+      const GEdges<D, kGRow> e(u, mu, dv, b + j0, m - j0);
       if constexpr (F::kDistStaged) {
         // the targets' dist, then the atomicMins, then the membership
         // atomics: one L2 round trip per step instead of one per edge and
@@ -427,14 +625,21 @@ __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
       const uint32_t lo = static_cast<uint32_t>(x);
       if (lo & OGS_EDGE_DOWN) continue;
       const uint32_t t = edge_dst(lo);
-      if (u.weight(x) == st.ld_dist(t)) {
+      D w0;
+      if constexpr (M::kOn) {
+        if (mu.has(b + j)) continue;
+        w0 = u.hop ? D(1) : D(mu.weight(b + j, x));
+      } else {
+        w0 = u.weight(x);
+      }
+      if (w0 == st.ld_dist(t)) {
         atomicOr(st.nh_word(j >> 5, t), 1u << (j & 31u));
         if (mem.first_push(t, r0)) fr.push(t, r0);
       }
     }
   }
   rounds(r0 + 1, fr.end_round<L2>(r0), [&](uint32_t v, uint32_t r) {
-    if (v == u.s || u.drained(v)) return;
+    if (v == u.s || drained(v)) return;
     const D dv = st.ld_dist(v);
     uint32_t nv[kUnrollW];  // NH(v); with a runtime word count re-read per edge
     if constexpr (W != kWRuntime) {
@@ -444,7 +649,7 @@ __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
     const uint32_t b = u.gRow[v] - u.e0, m = u.gRow[v + 1] - u.e0 - b;
     constexpr int kB = F::kNhStep;
     for (uint32_t j0 = 0; j0 < m; j0 += kB) {
-      const GEdges<D, kB> e(u, dv, b + j0, m - j0);
+      const GEdges<D, kB> e(u, mu, dv, b + j0, m - j0);
       if constexpr (F::kNhStaged) {
         bool ok[kB], add[kB];
 #pragma unroll
@@ -505,10 +710,14 @@ uint32_t global_lds3_bytes(uint32_t Sn) { return Sn * 8u + 4u * ((Sn + 31u) / 32
 // route_global_kernel would from the HBM rows: the launch no longer reads
 // its own dist / next-hop rows back (G1: 64 x 20k x 8 B of the 44 MB the PMC
 // counted per launch pair, profiles/r05_pmc_g1.json).
+// M: the mods policy, as for spf_global_kernel (the what-if launch passes no
+// prefix table: its route pass is route_global_diff_kernel).
+template <class M = NoMods, class... MA>
 __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
     ogs_graph g, const ogs_unit* __restrict__ units, uint32_t flags,
     uint32_t* __restrict__ oDist, uint32_t* __restrict__ oNh, uint32_t* __restrict__ scratch,
-    ogs_prefix_table pt, ogs_spf_out out) {
+    ogs_prefix_table pt, ogs_spf_out out, MA... ma) {
+  static_assert(sizeof...(MA) == (M::kOn ? 1 : 0), "the policy's arguments, or none");
   constexpr uint32_t kInf = 0xFFFFFFFFu;
   const int tid = threadIdx.x;
   const uint32_t u0 = blockIdx.x;
@@ -522,6 +731,10 @@ __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
   const uint64_t* __restrict__ edges = g.edges + e0;
   const uint8_t* __restrict__ nflags = g.node_flags + nb;
   const bool hop = (flags & OGS_F_HOP_METRIC) != 0;
+  M mu;
+  if constexpr (M::kOn) {
+    if (!mu.setup(ma..., g, GUnit<uint32_t>(g, unit, flags))) return;
+  }
   uint32_t* q0 = scratch + u0 * 3 * Sn + Sn;
   uint32_t* q1 = q0 + Sn;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -549,7 +762,11 @@ __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
     __syncthreads();
     for (uint32_t i = tid; i < n; i += kGBlock) {
       const uint32_t v = i == uint32_t(tid) ? v0 : ld_state<true>(cur + i);
-      if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
+      if constexpr (M::kOn) {
+        if (v != s && mu.drained(v)) continue;
+      } else {
+        if (v != s && (nflags[v] & OGS_NODE_OVERLOADED)) continue;  // 741-752
+      }
       const uint64_t xv = dn[v];
       const uint32_t dv = static_cast<uint32_t>(xv), nv = static_cast<uint32_t>(xv >> 32);
       const uint32_t b = gRow[v] - e0, m = gRow[v + 1] - e0 - b;
@@ -559,12 +776,24 @@ __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
         for (int k = 0; k < kGRow; ++k) {
           x[k] = j0 + k < m ? edges[b + j0 + k] : uint64_t(OGS_EDGE_DOWN);
         }
+        uint64_t b0 = 0, b1 = 0;  // the step's {dead, overridden} words
+        if constexpr (M::kOn) {
+          b0 = mu.word((b + j0) >> 5);
+          b1 = mu.word((b + (j0 + kGRow < m ? j0 + kGRow : m) - 1u) >> 5);
+        }
 #pragma unroll
         for (int k = 0; k < kGRow; ++k) {
           const uint32_t lo = static_cast<uint32_t>(x[k]);
           if (lo & OGS_EDGE_DOWN) continue;
           const uint32_t t = edge_dst(lo);
-          const uint32_t c = dv + (hop ? 1u : static_cast<uint32_t>(x[k] >> 32));
+          uint32_t wk = hop ? 1u : static_cast<uint32_t>(x[k] >> 32);
+          if constexpr (M::kOn) {
+            const uint32_t e = b + j0 + k, bit = 1u << (e & 31u);
+            const uint64_t bw = (e >> 5) == ((b + j0) >> 5) ? b0 : b1;
+            if (static_cast<uint32_t>(bw) & bit) continue;  // dead in this unit
+            if (static_cast<uint32_t>(bw >> 32) & bit) wk = mu.search(e);
+          }
+          const uint32_t c = dv + wk;
           // the source contributes its link slot, every other node NH(v)
           // (a source slot past bit 31 is not in a one-word set: dropped, as
           // the two-phase forms drop slots >= 32 W)
@@ -694,9 +923,9 @@ hipError_t launch_global_w(const ogs_graph& g, const ogs_prefix_table* pt,
       if (form == 1 && sync && lds3 <= kLds) {
         // the route pass runs inside the launch (no separate route kernel)
         const ogs_prefix_table ptv = pt ? *pt : ogs_prefix_table{};
-        return launch_dyn_lds(spf_global_lds3_kernel, dim3(nUnits), dim3(kGBlock), lds3, stream,
-                              g, units, flags, reinterpret_cast<uint32_t*>(dist), nh, scratch,
-                              ptv, out);
+        return launch_dyn_lds(spf_global_lds3_kernel<NoMods>, dim3(nUnits), dim3(kGBlock), lds3,
+                              stream, g, units, flags, reinterpret_cast<uint32_t*>(dist), nh,
+                              scratch, ptv, out);
       }
     }
     if ((form == 1 || form == 3) && sync && lds2 <= kLds) {
@@ -746,6 +975,117 @@ hipError_t launch_spf_routes_global(const ogs_graph& g, const ogs_prefix_table* 
     return launch_global_d<uint64_t>(g, pt, units, nUnits, flags, W, out, stream);
   }
   return launch_global_d<uint32_t>(g, pt, units, nUnits, flags, W, out, stream);
+}
+
+// ---- ogs_spf_routes_whatif_global ------------------------------------------
+// Can the global what-if form take this area? (u32 distances, W = 1, 2 or 4)
+bool whatif_global_takes(const ogs_graph& g, uint32_t flags, int W) {
+  return !(flags & OGS_F_WIDE_METRIC) && (W == 1 || W == 2 || W == 4) && g.max_nodes > 0 &&
+      uint32_t(g.max_nodes) <= OGS_MAX_NODES_PER_TOPO;
+}
+
+// One launch of the global-state SPF with the mods policy over every unit (the
+// state form chosen as launch_global_w chooses it), then the route and diff
+// pass. Workspace per unit: openr_gpu.h states it.
+template <int W>
+hipError_t launch_whatif_global_w(const ogs_graph& g, const ogs_prefix_table& pt,
+                                  const ogs_unit* units, int nUnits,
+                                  const ogs_whatif_mods& mods, const ogs_route_diff* diff,
+                                  uint32_t flags, const ogs_spf_out& out, hipStream_t stream) {
+  const size_t Sn = size_t(g.max_nodes), U = size_t(nUnits), Sp = size_t(pt.max_prefixes);
+  const uint32_t ew = (uint32_t(std::max(g.max_edges, 0)) + 31u) / 32u;
+  const uint32_t SnB = (uint32_t(Sn) + 3u) & ~3u;
+  const bool nodes = mods.node_off != nullptr;
+  const size_t distBytes = out.dist ? 0 : round256(U * Sn * 4);
+  const size_t nhBytes = out.nh ? 0 : round256(U * W * Sn * 4);
+  const size_t listBytes = round256(U * 3 * Sn * 4);
+  const size_t bitBytes = round256(U * size_t(ew) * 8);
+  const size_t rowBytes = nodes ? round256(U * size_t(SnB)) : 0;
+  void* ws = nullptr;
+  hipError_t e = workspace(distBytes + nhBytes + listBytes + bitBytes + rowBytes + round256(U * 4),
+                           stream, &ws);
+  if (e != hipSuccess) return e;
+  char* base = static_cast<char*>(ws);
+  uint32_t* dist = out.dist ? static_cast<uint32_t*>(out.dist) : reinterpret_cast<uint32_t*>(base);
+  uint32_t* nh = out.nh ? out.nh : reinterpret_cast<uint32_t*>(base + distBytes);
+  char* at = base + distBytes + nhBytes;
+  uint32_t* scratch = reinterpret_cast<uint32_t*>(at);
+  at += listBytes;
+  uint64_t* bits = reinterpret_cast<uint64_t*>(at);
+  at += bitBytes;
+  uint8_t* frows = nodes ? reinterpret_cast<uint8_t*>(at) : nullptr;
+  at += rowBytes;
+  uint32_t* skip = reinterpret_cast<uint32_t*>(at);
+  if (diff) {
+    e = hipMemsetAsync(diff->changed, 0, U * ((Sp + 31) / 32) * 4, stream);
+    if (e != hipSuccess) return e;
+  }
+  const bool changedOnly = (flags & OGS_F_CHANGED_ONLY) != 0;
+  // Exit-only units at one next-hop word only: OGS_F_CHANGED_ONLY is an
+  // nh_words == 1 mode (the entry refuses it otherwise), diff->base_nh is one
+  // [S_n] row, and the exit's copy of the base rows below is a one-word copy.
+  const bool exits = W == 1 && (flags & OGS_F_INCREMENTAL) && changedOnly && diff &&
+      diff->base_dist && g.edge_src;
+  GWhatifArgs a{};
+  a.mods = mods;
+  if (!mods.metric_off) a.mods.max_metric_per_unit = 0u;
+  a.edgeSrc = exits ? g.edge_src : nullptr;
+  a.baseDist = exits ? diff->base_dist : nullptr;
+  a.baseNh = exits ? diff->base_nh : nullptr;
+  a.exitDist = exits ? static_cast<uint32_t*>(out.dist) : nullptr;
+  a.exitNh = exits && diff->base_nh ? out.nh : nullptr;
+  a.counts = diff ? diff->counts : nullptr;
+  a.bits = bits;
+  a.frows = frows;
+  a.skip = skip;
+  a.ew = ew;
+  a.SnB = SnB;
+  auto run = [&](auto k, uint32_t ldsBytes) {
+    return launch_dyn_lds(k, dim3(nUnits), dim3(kGBlock), ldsBytes, stream, g, units, flags, W,
+                          dist, nh, scratch, a);
+  };
+  // "spf_global_lds" chooses the state form as in launch_global_w.
+  // "spf_global_sync" does not apply: the units' bitset and flag rows are read
+  // with sc1 loads after drained stores, so every form here is an L2SYNC form
+  // (the fenced HbmState<.., false> of that A/B is never taken).
+  constexpr uint32_t kLds = 160u * 1024u;
+  const int form = opts().spfGlobalLds;
+  const uint32_t lds = global_lds_bytes(uint32_t(Sn), 4);
+  const uint32_t lds2 = global_lds2_bytes(uint32_t(Sn), 4, W);
+  const uint32_t lds3 = global_lds3_bytes(uint32_t(Sn));
+  // (the one-phase kernel gets no prefix table: the route pass is its own launch)
+  if (W == 1 && form == 1 && lds3 <= kLds) {
+    if constexpr (W == 1) {
+      e = launch_dyn_lds(spf_global_lds3_kernel<WhatifRows, GWhatifArgs>, dim3(nUnits),
+                         dim3(kGBlock), lds3, stream, g, units, flags, dist, nh, scratch,
+                         ogs_prefix_table{}, ogs_spf_out{}, a);
+    }
+  } else if ((form == 1 || form == 3) && lds2 <= kLds) {
+    e = run(spf_global_kernel<LdsBothState<uint32_t, W>, WhatifRows, GWhatifArgs>, lds2);
+  } else if ((form == 1 || form == 2) && lds <= kLds) {
+    e = run(spf_global_kernel<LdsDistState<uint32_t, W>, WhatifRows, GWhatifArgs>, lds);
+  } else {
+    e = run(spf_global_kernel<HbmState<uint32_t, W, true>, WhatifRows, GWhatifArgs>, 0);
+  }
+  if (e != hipSuccess || Sp == 0) return e;
+  const ogs_route_diff d = diff ? *diff : ogs_route_diff{};
+  const unsigned by = unsigned((Sp + kBlock - 1) / kBlock);
+  auto rk = changedOnly ? route_global_diff_kernel<W, true> : route_global_diff_kernel<W, false>;
+  hipLaunchKernelGGL(rk, dim3(unsigned(nUnits), by), dim3(kBlock), 0, stream, g, pt, units, flags,
+                     dist, nh, skip, mods.node_off, frows, SnB, d, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_whatif_global(const ogs_graph& g, const ogs_prefix_table& pt,
+                                const ogs_unit* units, int nUnits, const ogs_whatif_mods& mods,
+                                const ogs_route_diff* diff, uint32_t flags, int W,
+                                const ogs_spf_out& out, hipStream_t stream) {
+  switch (W) {
+    case 1: return launch_whatif_global_w<1>(g, pt, units, nUnits, mods, diff, flags, out, stream);
+    case 2: return launch_whatif_global_w<2>(g, pt, units, nUnits, mods, diff, flags, out, stream);
+    case 4: return launch_whatif_global_w<4>(g, pt, units, nUnits, mods, diff, flags, out, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // ogs_routes_from_spf: route_global_kernel over caller-held SPF state.

@@ -2277,6 +2277,8 @@ PYBIND11_MODULE(_decision, m) {
              s.setMode(LinkFailureSweep::Mode(m));
            })
       .def("setListForm", &LinkFailureSweep::setListForm, py::arg("forceBitset"))
+      .def("setGlobalForm", &LinkFailureSweep::setGlobalForm, py::arg("forceGlobal"))
+      .def("setGlobalChunk", &LinkFailureSweep::setGlobalChunk, py::arg("n"))
       .def("launch", [](LinkFailureSweep& s, uintptr_t stream, bool records) {
              py::gil_scoped_release nogil;
              s.launch(reinterpret_cast<void*>(stream), records);
@@ -2321,6 +2323,7 @@ PYBIND11_MODULE(_decision, m) {
   m.attr("kRegisterList") = int(LinkFailureSweep::kRegisterList);
   m.attr("kEdgeBitset") = int(LinkFailureSweep::kEdgeBitset);
   m.attr("kTopologyCopies") = int(LinkFailureSweep::kTopologyCopies);
+  m.attr("kGlobalState") = int(LinkFailureSweep::kGlobalState);
 
   py::class_<VariantRunner>(m, "VariantRunner")
       .def(py::init<bool, bool>(), py::arg("enableV4") = true,

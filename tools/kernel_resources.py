@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel resource summary of the last `make` (build/kernels/*.o.ru, written
-by -Rpass-analysis=kernel-resource-usage): per kernel VGPRs, AGPRs, scratch
-bytes per lane and occupancy; kernels that spill to scratch are listed
+by -Rpass-analysis=kernel-resource-usage): per kernel VGPRs, AGPRs, SGPRs,
+scratch bytes per lane, static LDS bytes per block and occupancy; kernels that spill to scratch are listed
 first. A spill in a hot kernel is memory traffic and latency in its inner
 loop (round 6: spf_lds_route_kernel's 44 B/lane cost C3 4 %).
   python tools/kernel_resources.py [--all] [build/kernels/*.o.ru ...]"""
@@ -11,7 +11,8 @@ import subprocess
 import sys
 
 FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch",
-          "Occupancy [waves/SIMD]": "occ", "TotalSGPRs": "sgpr"}
+          "Occupancy [waves/SIMD]": "occ", "TotalSGPRs": "sgpr",
+          "LDS Size [bytes/block]": "lds"}
 
 
 def demangle(names):
@@ -47,7 +48,8 @@ def main():
     show = rows if "--all" in sys.argv else spill
     for r in sorted(show, key=lambda r: -r.get("scratch", 0)):
         print(f"  {r.get('scratch', 0):4d} B/lane  vgpr {r.get('vgpr', '?'):>3} agpr "
-              f"{r.get('agpr', '?'):>3} occ {r.get('occ', '?')}  {r['tu']}: {r['name'][:110]}")
+              f"{r.get('agpr', '?'):>3} sgpr {r.get('sgpr', '?'):>3} lds {r.get('lds', '?'):>5} "
+              f"occ {r.get('occ', '?')}  {r['tu']}: {r['name'][:110]}")
 
 
 if __name__ == "__main__":

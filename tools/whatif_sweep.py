@@ -18,7 +18,18 @@ buildRouteDb, calculateUpdate, restore -- on one thread over a 64-scenario
 stratified sample of each set, EXTRAPOLATED to the set's size; the sample's
 updates, counts and updated RouteDbs must equal the sweep's.
 
-  python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg]"""
+With --g1 the world is the G1 WAN (20,000 nodes, one prefix per node: past the
+LDS forms, so every set takes the global-state form, kGlobalState) and the
+sets are 2,000 scenarios each,
+  (h) every 10th node down,         (i) every 10th node drained,
+  (j) single-link failures,         (k) every 20th link cost out to 8x,
+  (l) every 20th link set to 1,
+each row also giving the share of exit-only units (no node bit, no lowered
+metric, no dead or raised edge tight in the base SPF: computed here on the
+host from the base SPF, the rule the kernel applies).
+
+  python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg]
+  python tools/whatif_sweep.py --g1 [--nodes 20000] [--sample 64] [--sets hijkl]"""
 import argparse
 import hashlib
 import json
@@ -32,15 +43,36 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
     sys.path.insert(0, p)
 
-FORMS = {0: "kRegisterList", 1: "kEdgeBitset", 2: "kTopologyCopies"}
+FORMS = {0: "kRegisterList", 1: "kEdgeBitset", 2: "kTopologyCopies", 3: "kGlobalState"}
+
+
+def fresh_world(base):
+    """a World whose prefix load is linear: every database goes into a FRESH
+    PrefixState, so no earlier advertisement has to be looked up and withdrawn
+    (tests/lsdb.py's sync lists the whole state per database)"""
+    class FreshWorld(base):
+        def load(self, M, me):
+            als = M.AreaLinkStates()
+            ls = als.add(self.area, me)
+            for d in self.adjdbs.values():
+                ls.updateAdjacencyDatabase(d, self.area)
+            ps = M.PrefixState()
+            for pdb in self.prefix_dbs:
+                for e in pdb["prefixEntries"]:
+                    ps.updatePrefix(pdb["thisNodeName"], self.area, e)
+            return als, ls, ps
+    return FreshWorld
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=0, help="override C4's node count (smoke runs)")
     ap.add_argument("--sample", type=int, default=64)
-    ap.add_argument("--sets", default="abcdefg", help="the sets to run, by letter")
+    ap.add_argument("--sets", default=None, help="the sets to run, by letter")
+    ap.add_argument("--g1", action="store_true", help="the G1 WAN and its sets (h .. l)")
     args = ap.parse_args()
+    if args.sets is None:
+        args.sets = "hijkl" if args.g1 else "abcdefg"
     import torch  # noqa: F401  (one HIP runtime: torch's)
     import _refcpu as O
     import openr_amd
@@ -50,11 +82,14 @@ def main():
                                      C4_VARIANTS)
     openr_amd.require_gpu()
     M = openr_amd.decision
-    opts = dict(C4_OPTS)
+    from openr_amd.workloads import G1_OPTS
+    opts = dict(G1_OPTS if args.g1 else C4_OPTS)
     if args.nodes:
         opts["nodes"] = args.nodes
     me = C4_SOURCE
     w = WM.as_metric_world(W.generated_world(M, "wan", opts))
+    if args.g1:
+        w = fresh_world(WM.MetricWorld)(list(w.adjdbs.values()), w.prefix_dbs, w.area)
     names = sorted(n for n in w.adjdbs if n != me)
     links = sorted({min((n, a["ifName"]), (a["otherNodeName"], a["otherIfName"]))
                     for n, d in w.adjdbs.items() for a in d["adjacencies"]})
@@ -81,11 +116,47 @@ def main():
         ("g: link set to 1", [{"linkMetrics": both(n, i, lambda x: 1)} for n, i in links], False,
          (2, 0)),
     ]
+    every = lambda xs, n: xs[::max(1, len(xs) // n)][:n]  # noqa: E731
+    sets += [
+        ("h: every 10th node down", [{"nodesDown": [n]} for n in names[::10]], False, (2,)),
+        ("i: every 10th node drained", [{"nodesDrained": [n]} for n in names[::10]], False, (2,)),
+        ("j: single-link failures", [{"links": [l]} for l in every(links, 2000)], False, (2,)),
+        ("k: every 20th link x8", [{"linkMetrics": both(n, i, lambda x: 8 * x)}
+                                   for n, i in links[::20]], False, (2,)),
+        ("l: every 20th link to 1", [{"linkMetrics": both(n, i, lambda x: 1)}
+                                     for n, i in links[::20]], False, (2,)),
+    ]
     sets = [s for s in sets if s[0][0] in args.sets]
-    print(f"what-if sweep, C4 WAN: {len(w.adjdbs)} nodes, {w.directed_edges()} directed edges, "
+    print(f"what-if sweep, {'G1' if args.g1 else 'C4'} WAN: {len(w.adjdbs)} nodes, "
+          f"{w.directed_edges()} directed edges, "
           f"source {me}, mode kChangedOnly unless a row says kFull")
     als, ls, ps = w.load(M, me)
     oracle = W.Oracle(O, w, me)
+    base, weight, far = {}, {}, {}  # the exit-only rule's inputs: the G1 rows alone
+    if args.g1:
+        base = {n: r[0] for n, r in oracle.ls.getSpfResult(me).items()}  # reached nodes' distances
+        # (node, ifName) -> the link's SPF weight, its other end
+        for n, d in w.adjdbs.items():
+            for a in d["adjacencies"]:
+                weight[(n, a["ifName"])] = both(n, a["ifName"], lambda x: x)[0][2]
+                far[(n, a["ifName"])] = (a["otherNodeName"], a["otherIfName"])
+
+    def exit_only(sc):
+        """the kernel's rule for a unit that runs nothing, from the base SPF
+        (the G1 sets' scenario kinds; the world has no link down)"""
+        if sc.get("nodesDrained") or sc.get("nodesSoftDrained"):
+            return False
+
+        def tight(n, ifn):  # either direction of the link behind (n, ifn)
+            return any(a in base and (a == me or not w.adjdbs[a].get("isOverloaded")) and
+                       base[a] + weight[(a, i)] == base.get(far[(a, i)][0])
+                       for a, i in ((n, ifn), far[(n, ifn)]))
+        dead = list(sc.get("links", ())) + [(n, a["ifName"]) for n in sc.get("nodesDown", ())
+                                            for a in w.adjdbs[n]["adjacencies"]]
+        if any(tight(n, i) for n, i in dead):
+            return False
+        return not any(m < weight[(n, i)] or (m > weight[(n, i)] and tight(n, i))
+                       for n, i, m in sc.get("linkMetrics", ()))
     out = []
     for label, scs, ab, modes in sets:
         sweeps, names = [], []  # one sweep and its row label per (mode, list form)
@@ -119,13 +190,16 @@ def main():
                        sweep_ms=median(ms[k][2:]), materialize_ms=mat_ms, changed_routes=n,
                        cpu_ms_per_scenario=cpu_ms, cpu_ms_extrapolated=cpu_ms * len(scs),
                        sample=len(idx), sample_digest=digest.hexdigest()[:16])
+            if args.g1:
+                row["exit_only_share"] = sum(exit_only(sc) for sc in scs) / len(scs)
             out.append(row)
             print(f"  {row['set']:26s} {len(scs):6d} scenarios  {row['form']:15s} "
                   f"launch+fetch {row['sweep_ms']:8.3f} ms  materialise {mat_ms:8.3f} ms  "
                   f"changed routes {n:9d}  | oracle loop {cpu_ms:7.3f} ms/scenario x "
                   f"{len(scs)} = {cpu_ms * len(scs) / 1e3:8.2f} s (extrapolated from "
-                  f"{len(idx)}); sample equal, sha1 {row['sample_digest']}")
-    print(json.dumps(dict(workload="c4_whatif_sweep", nodes=len(w.adjdbs), rows=out)))
+                  f"{len(idx)}); sample equal, sha1 {row['sample_digest']}" +
+                  (f"; exit-only units {100 * row['exit_only_share']:.1f} %" if args.g1 else ""))
+    print(json.dumps(dict(workload="g1_whatif_sweep" if args.g1 else "c4_whatif_sweep", nodes=len(w.adjdbs), rows=out)))
 
 
 if __name__ == "__main__":
