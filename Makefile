@@ -96,6 +96,16 @@ $(ASAN_WHATIF): $(HOST) $(HOST_H) tests/asan/whatif_asan.cpp $(ASAN_STUBS)
 	  -o $@ -lpthread
 asan-whatif: $(ASAN_WHATIF)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_WHATIF)
+# the what-if sweep's restoring kinds (undrain, link-up, soft-undrain), same
+# stubs; `make asan-restore` builds and runs this program alone
+ASAN_RESTORE := build/asan/restore_asan
+$(ASAN_RESTORE): $(HOST) $(HOST_H) tests/asan/restore_asan.cpp $(ASAN_STUBS)
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
+	  $(HOST) tests/asan/restore_asan.cpp $(ASAN_STUBS) \
+	  -o $@ -lpthread
+asan-restore: $(ASAN_RESTORE)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_RESTORE)
 $(ASAN_REF): oracle/refcpu/refcpu.cpp oracle/refcpu/refcpu.h oracle/refcpu/bindings.cpp openr_amd/csrc/gen/topogen.h
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -fPIC -shared -I$(PY_INC) -I$(PYBIND_INC) \
@@ -113,4 +123,4 @@ clean:
 	rm -f $(LIB) $(MOD) $(STAMPS) $(CCONS) $(KOBJ) $(SOBJ)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean stamps asan asan-whatif
+.PHONY: all oracle clean stamps asan asan-whatif asan-restore

@@ -127,6 +127,12 @@ extern "C" {
  * changed routes (bit set in diff->changed); the other records of out->meta
  * / metric / mask / sel are left as they were. Needs OGS_F_INCREMENTAL. */
 #define OGS_F_CHANGED_ONLY 0x80u
+/* ogs_spf_routes_whatif / ogs_spf_routes_whatif_global (and their ogs_ctx_
+ * forms) only: the unit lists may RESTORE -- OGS_WHATIF_EDGE_UP in
+ * metric_vals, OGS_NODE_CLEAR_SHIFT in node_bits (see ogs_whatif_mods).
+ * Without it both entries read the lists as they did before the flag
+ * existed; every other entry ignores it. */
+#define OGS_F_RESTORE 0x100u
 
 /* CSR of T topologies. */
 typedef struct ogs_graph {
@@ -615,8 +621,41 @@ int ogs_spf_routes_scenarios(const ogs_graph* graph,
  *     OGS_WHATIF_REFUSED}, its `changed` row stays zero and it writes no
  *     record; the other units are unaffected. Such weights belong to the
  *     exact domain (ogs_spf_routes with OGS_F_WIDE_METRIC over a patched
- *     topology). */
+ *     topology).
+ * With OGS_F_RESTORE the same lists also PUT THINGS BACK (without the flag
+ * everything above holds byte for byte: a metric_vals entry >= 2^31 refuses
+ * the unit and node_bits is ORed in whole). What the kinds stand for:
+ *   link undrain / link up   the adjacency re-sent with isOverloaded = false
+ *                    (LinkState.cpp:574, Link::setOverloadFromNode :150): when
+ *                    Link::isUp() then holds the link relaxes again;
+ *   node undrain     the node's database re-sent with isOverloaded = false
+ *                    (LinkState.cpp:480, 309-333): it transits again (741-752)
+ *                    and is no longer filtered or deprioritised as an
+ *                    advertiser (SpfSolver.cpp:526-551);
+ *   node soft-undrain  nodeMetricIncrementVal = 0 (LinkMonitor.cpp:971-1001):
+ *                    metric overrides on the node's links and its
+ *                    OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC bits cleared.
+ * Encodings, read under OGS_F_RESTORE only:
+ *   OGS_WHATIF_EDGE_UP in a metric_vals entry: the edge is UP in this unit
+ *     whatever its OGS_EDGE_DOWN bit in the CSR, with weight val & 0x7FFFFFFF
+ *     (1 .. 2^31 - 1; a masked weight of 0 refuses the unit as above). On an
+ *     edge that is up already it is a plain override. The caller lists BOTH
+ *     directed edges of the link. An edge in the dead list stays dead; ids >=
+ *     the edge count are skipped before anything is indexed. Under
+ *     OGS_F_HOP_METRIC the weights stay ignored (no unit is refused for one)
+ *     but the up flag is honoured.
+ *   OGS_NODE_CLEAR_SHIFT: bits (node_bits >> 4) & 0x7 are cleared from the
+ *     node's flags first, then the low nibble is ORed in.
+ * No new bitset: a revived edge rides in the unit's metric slice, so the LDS
+ * and workspace rules of both entries stay as written below and
+ * max_metric_per_unit counts the revived edges too. A unit that revives an edge
+ * that is down in the CSR, or clears OGS_NODE_OVERLOADED on a node that
+ * carries it, recomputes from the source inside the repair kernel (like one
+ * that lowers a metric) and takes no exit-only path in the global form.
+ * Clear nibbles are node bits: the full frontier form does not build them. */
 #define OGS_WHATIF_REFUSED 0xFFFFFFFFu
+#define OGS_WHATIF_EDGE_UP 0x80000000u
+#define OGS_NODE_CLEAR_SHIFT 4
 typedef struct ogs_whatif_mods {
   const uint32_t* dead_off;     /* [n_units + 1] device, ascending          */
   const uint32_t* dead_edges;   /* as ogs_scenario_mods                     */

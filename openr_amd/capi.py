@@ -40,6 +40,10 @@ EXPORTS = [
 ]
 
 OGS_WHATIF_REFUSED = 0xFFFFFFFF
+# the what-if entries' restorations (read under OGS_F_RESTORE only)
+OGS_F_RESTORE = 0x100
+OGS_WHATIF_EDGE_UP = 0x80000000
+OGS_NODE_CLEAR_SHIFT = 4
 
 
 class WhatifMods(ctypes.Structure):

@@ -1232,6 +1232,21 @@ class LinkFailureSweep {
   //                (after the scenario's own linkMetrics), and route selection
   //                reads the value (SpfSolver.cpp:511-551). The source may be
   //                soft-drained
+  // and the other half of a maintenance, each the mirror image of the above:
+  //  linksUndrained  that one adjacency re-sent with isOverloaded = false
+  //                (LinkState.cpp:574, Link::setOverloadFromNode :150): the
+  //                link comes up only if Link::isUp() then holds (the other
+  //                end not overloaded, or named too, and the link usable)
+  //  nodesUndrained  the node's database re-sent with isOverloaded = false
+  //                (LinkState.cpp:480, 309-333): it transits again and is no
+  //                longer filtered or deprioritised as an advertiser
+  //                (SpfSolver.cpp:526-551). The source may be named
+  //  nodesSoftUndrained  the database re-sent with nodeMetricIncrementVal = 0
+  //                (LinkMonitor.cpp:971-1001): every adjacency metric of the
+  //                node becomes published - current increment (after the
+  //                scenario's own linkMetrics)
+  // Links that do not exist in the LinkState cannot be brought up: the CSR's
+  // structure does not change.
   struct LinkMetric {  // (node, its interface) and the metric it now sends
     std::string node, ifName;
     int64_t metric{1};
@@ -1245,6 +1260,8 @@ class LinkFailureSweep {
     std::vector<std::string> nodesDown, nodesDrained;
     std::vector<LinkMetric> linkMetrics;
     std::vector<SoftDrain> nodesSoftDrained;
+    std::vector<LinkDown> linksUndrained;  // (node, its interface)
+    std::vector<std::string> nodesUndrained, nodesSoftUndrained;
   };
   // A scenario over the flat topology: dead DIRECTED edge ids (both
   // directions of every up link named or touching a downed node) and drained
@@ -1258,16 +1275,31 @@ class LinkFailureSweep {
   // the OGS_NODE_* bits the scenario adds to each (hard drain:
   // OGS_NODE_OVERLOADED, soft drain: OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC),
   // bits the node carries already left out.
+  // revivedEdges / revivedVals: both directed edges of every link that is down
+  // now and up in the scenario, ascending, with the link's weight after the
+  // scenario's metric changes (never in metricEdges: those are up links).
+  // clearedNodes / clearedBits: nodes, ascending, and the OGS_NODE_* bits the
+  // scenario takes off each (undrain: OGS_NODE_OVERLOADED, soft-undrain:
+  // OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC), bits the node lacks left out.
+  // A link that stays down or is up already, a node that is not overloaded
+  // and a node with increment 0 are no-ops.
   struct Expanded {
     std::vector<uint32_t> deadEdges, drainedNodes;
     std::vector<uint32_t> metricEdges;
     std::vector<uint64_t> metricVals;
     std::vector<uint32_t> flagNodes;
     std::vector<uint8_t> flagBits;
+    std::vector<uint32_t> revivedEdges;
+    std::vector<uint64_t> revivedVals;
+    std::vector<uint32_t> clearedNodes;
+    std::vector<uint8_t> clearedBits;
   };
   // std::invalid_argument: an unknown node or link, `me` in nodesDown, a node
-  // in both nodesDown and nodesDrained or nodesSoftDrained, an increment < 1.
-  // Host only.
+  // in both nodesDown and nodesDrained or nodesSoftDrained, an increment < 1;
+  // a node in nodesDown that is also named by linksUndrained, nodesUndrained
+  // or nodesSoftUndrained; the same node in nodesDrained and nodesUndrained, or
+  // in nodesSoftDrained and nodesSoftUndrained; the same link, by either end,
+  // in linksDown and linksUndrained. Host only.
   static Expanded expandScenario(const LinkState& ls, const std::string& me, const Scenario& sc);
   LinkFailureSweep(const std::string& myNodeName, const LinkState& ls,
                    const PrefixState& ps, const std::vector<Scenario>& scenarios,
@@ -1276,7 +1308,9 @@ class LinkFailureSweep {
   // How a launch holds "what is removed": kRegisterList every scenario has at
   // most 8 dead directed edges and no drain (ogs_spf_routes_variants);
   // kEdgeBitset ogs_spf_routes_scenarios (LDS bitset, drained-flag row), or
-  // ogs_spf_routes_whatif when a scenario carries a metric or a soft drain;
+  // ogs_spf_routes_whatif when a scenario carries a metric, a soft drain or a
+  // restoration (with OGS_F_RESTORE only when some scenario restores; cleared
+  // bits are node bits: kFull mode or W > 1 takes them to kTopologyCopies);
   // kTopologyCopies one patched topology per scenario through ogs_spf_routes
   // (zero / negative / 64-bit metrics, W > 4, and what the scenarios entry
   // or what-if entry reports unsupported: drains / soft drains in kFull mode,
@@ -1370,6 +1404,12 @@ class LinkFailureSweep {
   std::vector<uint32_t> metricOff_{0}, metricEdge_, flagOff_{0}, flagNode_;
   std::vector<uint64_t> metricVal_;
   std::vector<uint8_t> flagBits_;
+  // restores_: some scenario revives a link or clears a node bit. Then
+  // metricUp_[i] marks the revived entries of metricEdge_ (uploaded with
+  // OGS_WHATIF_EDGE_UP) and flagBits_ carry the cleared bits in the high
+  // nibble (OGS_NODE_CLEAR_SHIFT); launches set OGS_F_RESTORE
+  std::vector<uint8_t> metricUp_;
+  bool restores_{false};
   uint32_t maxMetricList_{0};
   bool whatif_{false};
   DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_, dFlagOff_, dFlagNode_, dFlagBits_;

@@ -104,9 +104,12 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
       if (f.edgeLink[r] == link) x.deadEdges.push_back(r);
     }
   };
+  std::set<const Link*> namedDown;
   for (const auto& d : sc.linksDown) {
     const uint32_t u = nodeId(d.node);
-    kill(u, edgeOf(u, d.node, d.ifName));
+    const uint32_t e = edgeOf(u, d.node, d.ifName);
+    namedDown.insert(f.edgeLink[e]);
+    kill(u, e);
   }
   std::vector<uint32_t> down;
   for (const auto& n : sc.nodesDown) {
@@ -121,6 +124,32 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
       throw std::invalid_argument("LinkFailureSweep: " + n + " both down and drained");
     }
     if (!(f.nodeFlags[u] & OGS_NODE_OVERLOADED)) x.drainedNodes.push_back(u);
+  }
+  // ---- restorations: the overload bit off an adjacency or a node -----------
+  auto notDown = [&](uint32_t u, const std::string& n, const char* what) {
+    if (std::find(down.begin(), down.end(), u) != down.end()) {
+      throw std::invalid_argument("LinkFailureSweep: " + n + " both down and " + what);
+    }
+  };
+  std::map<const Link*, unsigned> undrained;  // sides re-sent with isOverloaded = false
+  for (const auto& d : sc.linksUndrained) {
+    const uint32_t u = nodeId(d.node);
+    const Link* l = f.edgeLink[edgeOf(u, d.node, d.ifName)];
+    notDown(u, d.node, "in linksUndrained");
+    if (namedDown.count(l)) {
+      throw std::invalid_argument("LinkFailureSweep: link " + d.node + "%" + d.ifName +
+                                  " both down and undrained");
+    }
+    undrained[l] |= d.node == l->firstNodeName() ? 1u : 2u;
+  }
+  std::map<uint32_t, uint8_t> cleared;
+  for (const auto& n : sc.nodesUndrained) {
+    const uint32_t u = nodeId(n);
+    notDown(u, n, "undrained");
+    if (std::find(sc.nodesDrained.begin(), sc.nodesDrained.end(), n) != sc.nodesDrained.end()) {
+      throw std::invalid_argument("LinkFailureSweep: " + n + " both drained and undrained");
+    }
+    if (f.nodeFlags[u] & OGS_NODE_OVERLOADED) cleared[u] |= uint8_t(OGS_NODE_OVERLOADED);
   }
   for (auto* l : {&x.deadEdges, &x.drainedNodes}) {  // the same link named twice folds
     std::sort(l->begin(), l->end());
@@ -180,23 +209,71 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
     const uint8_t add = uint8_t((OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC) & ~f.nodeFlags[u]);
     if (add) bits[u] |= add;
   }
-  std::vector<std::pair<uint32_t, uint64_t>> over;
-  for (const auto& [l, mv] : moved) {
-    if (!l->isUp() || killed.count(l)) continue;  // down stays down
-    const LinkStateMetric w = std::max(mv.m[0], mv.m[1]);
-    if (w == l->getMaxMetric()) continue;  // the link's weight stays: a no-op
+  std::set<uint32_t> softOff;
+  for (const auto& n : sc.nodesSoftUndrained) {
+    const uint32_t u = nodeId(n);
+    notDown(u, n, "soft-undrained");
+    if (soft.count(u)) {
+      throw std::invalid_argument("LinkFailureSweep: " + n +
+                                  " both soft-drained and soft-undrained");
+    }
+    if (!softOff.insert(u).second) continue;  // named twice: once
+    const uint64_t inc = ls.getNodeMetricIncrement(n);
+    if (inc == 0) continue;  // nothing to take off
+    // LinkMonitor.cpp:1001: published - the increment it carries
+    for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) {
+      sideMetric(f.edgeLink[e], n) -= static_cast<LinkStateMetric>(inc);
+    }
+    const uint8_t off = uint8_t((OGS_NODE_SOFTDRAIN | OGS_NODE_METRICINC) & f.nodeFlags[u]);
+    if (off) cleared[u] |= off;
+  }
+  // both directed edges of link l with weight w
+  auto bothEdges = [&](const Link* l, uint64_t w, std::vector<std::pair<uint32_t, uint64_t>>& to) {
     for (const std::string* n : {&l->firstNodeName(), &l->secondNodeName()}) {
       const uint32_t u = f.id.at(*n);
       for (uint32_t e = f.rowPtr[u]; e < f.rowPtr[u + 1]; ++e) {
-        if (f.edgeLink[e] == l) over.emplace_back(e, w);
+        if (f.edgeLink[e] == l) to.emplace_back(e, w);
       }
     }
+  };
+  std::vector<std::pair<uint32_t, uint64_t>> over, revived;
+  for (const auto& [l, mv] : moved) {
+    if (!l->isUp() || killed.count(l)) continue;  // down stays down (or comes up, below)
+    const LinkStateMetric w = std::max(mv.m[0], mv.m[1]);
+    if (w == l->getMaxMetric()) continue;  // the link's weight stays: a no-op
+    bothEdges(l, w, over);
   }
-  std::sort(over.begin(), over.end());
-  over.erase(std::unique(over.begin(), over.end()), over.end());
+  // a link comes up when Link::isUp() holds with the named ends' bits off; one
+  // that touches a downed node stays withdrawn
+  for (const auto& [l, sides] : undrained) {
+    if (l->isUp()) continue;  // up already: a no-op
+    const bool ov0 = l->getOverloadFromNode(l->firstNodeName()) && !(sides & 1u);
+    const bool ov1 = l->getOverloadFromNode(l->secondNodeName()) && !(sides & 2u);
+    if (ov0 || ov1 || !l->getUsability()) continue;  // stays down: a no-op
+    bool gone = false;
+    for (const std::string* n : {&l->firstNodeName(), &l->secondNodeName()}) {
+      gone |= std::find(down.begin(), down.end(), f.id.at(*n)) != down.end();
+    }
+    if (gone) continue;
+    const auto it = moved.find(l);
+    bothEdges(l, it == moved.end() ? l->getMaxMetric() : std::max(it->second.m[0], it->second.m[1]),
+              revived);
+  }
+  for (auto* l : {&over, &revived}) {
+    std::sort(l->begin(), l->end());
+    l->erase(std::unique(l->begin(), l->end()), l->end());
+  }
   for (const auto& [e, w] : over) {
     x.metricEdges.push_back(e);
     x.metricVals.push_back(w);
+  }
+  for (const auto& [e, w] : revived) {
+    x.revivedEdges.push_back(e);
+    x.revivedVals.push_back(w);
+  }
+  for (const auto& [u, b] : cleared) {
+    x.clearedNodes.push_back(u);
+    x.clearedBits.push_back(b);
   }
   for (const auto& [u, b] : bits) {
     x.flagNodes.push_back(u);
@@ -261,7 +338,11 @@ void LinkFailureSweep::setGlobalChunk(size_t n) {
 void LinkFailureSweep::uploadWhatifLists() {
   if (whatifUploaded_ || exact_) return;
   whatifUploaded_ = true;
-  std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());  // all within 32 bits
+  // all within 31 bits (the domain guards sent anything else to copies)
+  std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());
+  for (size_t i = 0; i < vals.size(); ++i) {
+    if (metricUp_[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
+  }
   dMetricOff_.upload(metricOff_.data(), metricOff_.size());
   dMetricEdge_.upload(metricEdge_.data(), metricEdge_.size());
   dMetricVal_.upload(vals.data(), vals.size());
@@ -368,15 +449,35 @@ LinkFailureSweep::LinkFailureSweep(
     deadOff_.push_back(uint32_t(deadList_.size()));
     drainOff_.push_back(uint32_t(drainList_.size()));
     maxDead_ = std::max(maxDead_, uint32_t(x.deadEdges.size()));
-    metricEdge_.insert(metricEdge_.end(), x.metricEdges.begin(), x.metricEdges.end());
-    metricVal_.insert(metricVal_.end(), x.metricVals.begin(), x.metricVals.end());
-    flagNode_.insert(flagNode_.end(), x.flagNodes.begin(), x.flagNodes.end());
-    flagBits_.insert(flagBits_.end(), x.flagBits.begin(), x.flagBits.end());
+    // the unit's metric slice: overrides and revived edges (disjoint: an
+    // override is of an up link), merged ascending by edge id
+    for (size_t i = 0, j = 0; i < x.metricEdges.size() || j < x.revivedEdges.size();) {
+      const bool rev = i == x.metricEdges.size() ||
+          (j < x.revivedEdges.size() && x.revivedEdges[j] < x.metricEdges[i]);
+      metricEdge_.push_back(rev ? x.revivedEdges[j] : x.metricEdges[i]);
+      metricVal_.push_back(rev ? x.revivedVals[j] : x.metricVals[i]);
+      metricUp_.push_back(rev ? 1 : 0);
+      ++(rev ? j : i);
+    }
+    // its node list: one entry a node, set bits low, cleared bits high
+    {
+      std::map<uint32_t, uint8_t> nb;
+      for (size_t i = 0; i < x.flagNodes.size(); ++i) nb[x.flagNodes[i]] |= x.flagBits[i];
+      for (size_t i = 0; i < x.clearedNodes.size(); ++i) {
+        nb[x.clearedNodes[i]] |= uint8_t(x.clearedBits[i] << OGS_NODE_CLEAR_SHIFT);
+      }
+      for (const auto& [u, b] : nb) {
+        flagNode_.push_back(u);
+        flagBits_.push_back(b);
+      }
+    }
+    restores_ = restores_ || !x.revivedEdges.empty() || !x.clearedNodes.empty();
     metricOff_.push_back(uint32_t(metricEdge_.size()));
     flagOff_.push_back(uint32_t(flagNode_.size()));
-    maxMetricList_ = std::max(maxMetricList_, uint32_t(x.metricEdges.size()));
+    maxMetricList_ = std::max(maxMetricList_,
+                              uint32_t(x.metricEdges.size() + x.revivedEdges.size()));
   }
-  whatif_ = !metricEdge_.empty() ||
+  whatif_ = restores_ || !metricEdge_.empty() ||
       std::any_of(flagBits_.begin(), flagBits_.end(),
                   [](uint8_t b) { return (b & ~uint8_t(OGS_NODE_OVERLOADED)) != 0; });
   // the overrides' own domain guards: a zero / negative weight replays the
@@ -477,11 +578,29 @@ void LinkFailureSweep::exactLaunch(void* stream) {
       for (uint32_t i = metricOff_[t - 1]; i < metricOff_[t]; ++i) {
         uint64_t& w = hb.edges[e0 + metricEdge_[i]];
         w = (w & 0xFFFFFFFFull) | (uint64_t(uint32_t(metricVal_[i])) << 32);
+        // a revived link: up again with that weight (a dead edge stays dead)
+        const bool dead = std::binary_search(deadList_.begin() + deadOff_[t - 1],
+                                             deadList_.begin() + deadOff_[t], metricEdge_[i]);
+        if (metricUp_[i] && !dead) w &= ~uint64_t(OGS_EDGE_DOWN);
         hb.maxMetric = std::max(hb.maxMetric, metricVal_[i]);
         hb.hasZeroMetric |= metricVal_[i] == 0;
       }
+      // flag bits: cleared first, then set -- an undrain is the mirror image
+      // of the drain above (the flag, and OGS_EDGE_DST_OVERLOADED off every
+      // edge into the node)
       for (uint32_t i = flagOff_[t - 1]; i < flagOff_[t]; ++i) {
-        hb.nodeFlags[n0 + flagNode_[i]] |= flagBits_[i];
+        const uint32_t x = flagNode_[i];
+        const uint8_t clr = uint8_t((flagBits_[i] >> OGS_NODE_CLEAR_SHIFT) & 0x7u);
+        uint8_t& nf = hb.nodeFlags[n0 + x];
+        const bool was = (nf & OGS_NODE_OVERLOADED) != 0;
+        nf = uint8_t((nf & ~clr) | (flagBits_[i] & 0x0Fu));
+        if (!was || (nf & OGS_NODE_OVERLOADED)) continue;
+        for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
+          const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
+          for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
+            if (f.edgeLink[r] == f.edgeLink[e]) hb.edges[e0 + r] &= ~uint64_t(OGS_EDGE_DST_OVERLOADED);
+          }
+        }
       }
     }
     std::vector<ogs_unit> us(n);
@@ -584,6 +703,8 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   uint32_t fl = flags();
   if (mode_ != kFull) fl |= OGS_F_INCREMENTAL;
   if (changedOnly) fl |= OGS_F_CHANGED_ONLY;
+  // (restores_ implies whatif_: only the two what-if entries below see the flag)
+  if (restores_) fl |= OGS_F_RESTORE;
   if (form_ == kGlobalState) {
     globalLaunch(g, pt, diff, fl, out, stream);
   } else if (form_ == kRegisterList) {

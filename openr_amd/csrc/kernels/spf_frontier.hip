@@ -154,10 +154,8 @@ struct WhatifBits {
   __device__ __forceinline__ bool has(uint32_t x) const {
     return (static_cast<uint32_t>(bb[x >> 5]) >> (x & 31u)) & 1u;
   }
-  __device__ __forceinline__ uint32_t weight(uint32_t e, uint64_t x) const {
-    if (!((static_cast<uint32_t>(bb[e >> 5] >> 32) >> (e & 31u)) & 1u)) {
-      return static_cast<uint32_t>(x >> 32);
-    }
+  // the slice's value for overridden edge e (weight | OGS_WHATIF_EDGE_UP)
+  __device__ __forceinline__ uint32_t search(uint32_t e) const {
     uint32_t lo = 0, hi = n;  // n >= 1: a set bit came from the slice
     while (hi - lo > 1u) {
       const uint32_t mid = (lo + hi) >> 1;
@@ -165,7 +163,40 @@ struct WhatifBits {
     }
     return mv[lo];
   }
+  // (a unit that runs holds OGS_WHATIF_EDGE_UP only under OGS_F_RESTORE:
+  // without the flag such a value refused it)
+  __device__ __forceinline__ uint32_t weight(uint32_t e, uint64_t x) const {
+    if (!((static_cast<uint32_t>(bb[e >> 5] >> 32) >> (e & 31u)) & 1u)) {
+      return static_cast<uint32_t>(x >> 32);
+    }
+    return search(e) & ~OGS_WHATIF_EDGE_UP;
+  }
+  // is edge e (lo = its CSR word's low half) down in this unit: dead, or down
+  // in the CSR and not revived. The slice is searched only for edges that are
+  // down in the CSR and overridden, so a live edge costs the one LDS read.
+  __device__ __forceinline__ bool down(uint32_t e, uint32_t lo) const {
+    const uint64_t w = bb[e >> 5];
+    if ((static_cast<uint32_t>(w) >> (e & 31u)) & 1u) return true;
+    if (!(lo & OGS_EDGE_DOWN)) return false;
+    if (!((static_cast<uint32_t>(w >> 32) >> (e & 31u)) & 1u)) return true;
+    return !(search(e) & OGS_WHATIF_EDGE_UP);
+  }
 };
+
+// "edge e does not relax in this unit" for every walker: the CSR's down bit,
+// then the unit's dead set (MODS); a what-if unit may also have revived it
+template <bool MODS, typename Dead>
+__device__ __forceinline__ bool edge_down(const Dead& dead, uint32_t e, uint32_t lo) {
+  if constexpr (std::is_same_v<Dead, WhatifBits>) {
+    return dead.down(e, lo);
+  } else {
+    if (lo & OGS_EDGE_DOWN) return true;
+    if constexpr (MODS) {
+      if (dead.has(e)) return true;
+    }
+    return false;
+  }
+}
 
 template <bool MODS, typename Dead>
 __device__ __forceinline__ void load_chunk(const uint64_t* __restrict__ edges,
@@ -176,11 +207,16 @@ __device__ __forceinline__ void load_chunk(const uint64_t* __restrict__ edges,
 #pragma unroll
   for (uint32_t i = 0; i < kChunk; ++i) {
     x[i] = i < n ? edges[b + i] : uint64_t(OGS_EDGE_DOWN);
-    if constexpr (MODS) {
-      if (dead.has(b + i)) x[i] |= uint64_t(OGS_EDGE_DOWN);
-      if constexpr (std::is_same_v<Dead, WhatifBits>) {
-        if (i < n) x[i] = (x[i] & 0xFFFFFFFFull) | (uint64_t(dead.weight(b + i, x[i])) << 32);
+    if constexpr (std::is_same_v<Dead, WhatifBits>) {
+      // (past the chunk's count no bit or slice entry is this edge's: a revival
+      // of the next row's first edge must not bring a padding edge up)
+      if (i < n) {
+        const uint32_t lo = static_cast<uint32_t>(x[i]);
+        const uint32_t st = dead.down(b + i, lo) ? (lo | OGS_EDGE_DOWN) : (lo & ~OGS_EDGE_DOWN);
+        x[i] = uint64_t(st) | (uint64_t(dead.weight(b + i, x[i])) << 32);
       }
+    } else if constexpr (MODS) {
+      if (dead.has(b + i)) x[i] |= uint64_t(OGS_EDGE_DOWN);
     }
   }
 }
@@ -301,10 +337,7 @@ __device__ __forceinline__ void frontier_spf(
     for (uint32_t j = tid; j < n; j += B) {
       const uint64_t x = edges[b + j];
       const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      if constexpr (MODS) {
-        if (dead.has(b + j)) continue;
-      }
+      if (edge_down<MODS>(dead, b + j, lo)) continue;
       const uint32_t t = edge_dst(lo);
       const uint32_t c = hop ? 1u : dead.weight(b + j, x);
       if (c < dist[t]) {
@@ -360,10 +393,7 @@ __device__ __forceinline__ void frontier_spf(
     for (uint32_t j = tid; j < n && j < 32u * W; j += B) {
       const uint64_t x = edges[b + j];
       const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      if constexpr (MODS) {
-        if (dead.has(b + j)) continue;
-      }
+      if (edge_down<MODS>(dead, b + j, lo)) continue;
       const uint32_t t = edge_dst(lo);
       const uint32_t w = hop ? 1u : dead.weight(b + j, x);
       if (w == dist[t]) {
@@ -459,10 +489,7 @@ __device__ __forceinline__ void frontier_spf_packed(
     for (uint32_t j = tid; j < n; j += B) {
       const uint64_t x = edges[sb + j];
       const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      if constexpr (MODS) {
-        if (dead.has(sb + j)) continue;
-      }
+      if (edge_down<MODS>(dead, sb + j, lo)) continue;
       const uint32_t t = edge_dst(lo);
       const uint32_t c = hop ? 1u : dead.weight(sb + j, x);
       const uint32_t bits = j < 32u ? 1u << j : 0u;
@@ -626,10 +653,7 @@ __device__ __forceinline__ void queue_spf(
       const uint32_t dv = dist[v];
       for_row(edges, b, rowEnd - b, [&](uint32_t e, uint64_t x) {
         const uint32_t lo = static_cast<uint32_t>(x);
-        if (lo & OGS_EDGE_DOWN) return;
-        if constexpr (MODS) {
-          if (dead.has(e)) return;
-        }
+        if (edge_down<MODS>(dead, e, lo)) return;
         const uint32_t t = edge_dst(lo);
         const uint32_t c = dv + (hop ? 1u : dead.weight(e, x));
         if (c < dist[t] && c < atomicMin(&dist[t], c)) append(t, r);
@@ -652,10 +676,7 @@ __device__ __forceinline__ void queue_spf(
     for (uint32_t j = tid; j < m && j < 32u * W; j += kBlock) {
       const uint64_t x = edges[b + j];
       const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
-      if constexpr (MODS) {
-        if (dead.has(b + j)) continue;
-      }
+      if (edge_down<MODS>(dead, b + j, lo)) continue;
       const uint32_t t = edge_dst(lo);
       const uint32_t w = hop ? 1u : dead.weight(b + j, x);
       if (w == dist[t]) {
@@ -683,10 +704,7 @@ __device__ __forceinline__ void queue_spf(
       for (int w = 0; w < W; ++w) nv[w] = nh[v * W + w];
       for_row(edges, b, rowEnd - b, [&](uint32_t e, uint64_t x) {
         const uint32_t lo = static_cast<uint32_t>(x);
-        if (lo & OGS_EDGE_DOWN) return;
-        if constexpr (MODS) {
-          if (dead.has(e)) return;
-        }
+        if (edge_down<MODS>(dead, e, lo)) return;
         const uint32_t t = edge_dst(lo);
         if (dv + (hop ? 1u : dead.weight(e, x)) != dist[t]) return;
         bool add = false;
@@ -745,10 +763,7 @@ __device__ __forceinline__ uint32_t packed_rounds(
       const uint32_t nv = static_cast<uint32_t>(xv >> 32);
       for_row(edges, b, rowEnd - b, [&](uint32_t e, uint64_t x) {
         const uint32_t lo = static_cast<uint32_t>(x);
-        if (lo & OGS_EDGE_DOWN) return;
-        if constexpr (MODS) {
-          if (dead.has(e)) return;
-        }
+        if (edge_down<MODS>(dead, e, lo)) return;
         const uint32_t t = edge_dst(lo);
         const uint32_t c = dv + (hop ? 1u : dead.weight(e, x));
         // the source contributes the link slot (its row index), others NH(v)
@@ -904,8 +919,10 @@ __device__ __forceinline__ void spf_frontier_body(
     uint32_t* mv = me + mods.max_metric_per_unit;
     const uint32_t E = gRow[N] - e0;
     __shared__ uint32_t refused;
-    // (under OGS_F_HOP_METRIC the metric lists are ignored)
-    const bool metrics = mods.metric_off && !(flags & OGS_F_HOP_METRIC);
+    // (under OGS_F_HOP_METRIC the metric lists are ignored, but for the up
+    // flags of OGS_F_RESTORE)
+    const bool hopm = (flags & OGS_F_HOP_METRIC) != 0, restore = (flags & OGS_F_RESTORE) != 0;
+    const bool metrics = mods.metric_off && (!hopm || restore);
     const uint32_t m0 = metrics ? mods.metric_off[u0] : 0u;
     const uint32_t mn = metrics ? mods.metric_off[u0 + 1] - m0 : 0u;
     const bool tooLong = mn > mods.max_metric_per_unit;  // past the LDS the caller sized
@@ -923,8 +940,10 @@ __device__ __forceinline__ void spf_frontier_body(
       me[i] = e;
       mv[i] = v;
       if (e >= E) continue;  // skipped: sets no bit, so the search never returns it
-      if (v - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
-        refused = 1u;
+      if (hopm) {  // weights ignored: only a revival counts
+        if (!(v & OGS_WHATIF_EDGE_UP)) continue;
+      } else if ((restore ? v & ~OGS_WHATIF_EDGE_UP : v) - 1u >= 0x7FFFFFFFu) {
+        refused = 1u;  // 0 or >= 2^31: the exact domain's
         continue;
       }
       atomicOr(&bb32[2u * (e >> 5) + 1u], 1u << (e & 31u));
@@ -1539,6 +1558,12 @@ uint32_t repair_lds_bytes(uint32_t Sn) {
 // the source, the list = {source}, the same packed rounds -- queue_spf_packed's
 // start state over the arrays the repair already holds -- and inA all ones, so
 // the changed-only pass compares every prefix; 0 or >= 2^31 -> refused.
+// Under OGS_F_RESTORE a unit also recomputes from the source when it revives
+// an edge that is down in the CSR (OGS_WHATIF_EDGE_UP in its slice) or clears
+// OGS_NODE_OVERLOADED on a node that carries it (OGS_NODE_CLEAR_SHIFT): nodes
+// outside every base descendant set may get shorter paths, as for a lowered
+// metric. Its drained-ness comes from its own flag row; the base's flags keep
+// telling the base tight DAG.
 // (the statements: spf_repair_body.h)
 template <bool CHANGED_ONLY, bool LIST = false, bool DRAINS = false>
 __global__ __launch_bounds__(kBlock) void spf_variant_repair_kernel(

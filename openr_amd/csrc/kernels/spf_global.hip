@@ -117,10 +117,11 @@ struct GEdges {
         const uint64_t bw = ((e + k) >> 5) == (e >> 5) ? b0 : b1;
         const uint32_t bit = 1u << ((e + k) & 31u);
         const bool live = uint32_t(k) < left;  // past the row: no bit is this edge's
-        up[k] = !(lo & OGS_EDGE_DOWN) && !(live && (static_cast<uint32_t>(bw) & bit));
+        up[k] = live && !mu.down(e + k, lo, bw);
         t[k] = edge_dst(lo);
-        c[k] = dv + ((live && (static_cast<uint32_t>(bw >> 32) & bit)) ? D(mu.search(e + k))
-                                                                      : u.weight(x[k]));
+        c[k] = dv + ((!u.hop && live && (static_cast<uint32_t>(bw >> 32) & bit))
+                         ? D(MU::weight_of(mu.search(e + k)))
+                         : u.weight(x[k]));
       }
     } else {
 #pragma unroll
@@ -156,6 +157,7 @@ struct GWhatifArgs {
   uint8_t* frows;            // [U][SnB] the units' node-flag rows (nullptr: no node lists)
   uint32_t* skip;            // [U] 1: the unit ran no SPF (refused / exit-only)
   uint32_t ew, SnB;
+  bool restore;              // OGS_F_RESTORE: up flags and clear nibbles are read
 };
 
 // Per-unit HBM rows in the workspace, filled by the unit's workgroup before
@@ -185,9 +187,24 @@ struct WhatifRows {
     }
     return mv[lo];
   }
+  // (search() returns the slice's value: weight | OGS_WHATIF_EDGE_UP, the
+  // latter only under OGS_F_RESTORE -- without the flag it refused the unit)
+  static __device__ __forceinline__ uint32_t weight_of(uint32_t val) {
+    return val & ~OGS_WHATIF_EDGE_UP;
+  }
   __device__ __forceinline__ uint32_t weight(uint32_t e, uint64_t x) const {
     return ((static_cast<uint32_t>(word(e >> 5) >> 32) >> (e & 31u)) & 1u)
-        ? search(e) : static_cast<uint32_t>(x >> 32);
+        ? weight_of(search(e)) : static_cast<uint32_t>(x >> 32);
+  }
+  // is edge e (lo: its CSR word's low half, bw: its {dead, overridden} word)
+  // down in this unit: dead, or down in the CSR and not revived. The slice is
+  // searched only for edges down in the CSR and overridden.
+  __device__ __forceinline__ bool down(uint32_t e, uint32_t lo, uint64_t bw) const {
+    const uint32_t bit = 1u << (e & 31u);
+    if (static_cast<uint32_t>(bw) & bit) return true;
+    if (!(lo & OGS_EDGE_DOWN)) return false;
+    if (!(static_cast<uint32_t>(bw >> 32) & bit)) return true;
+    return !(search(e) & OGS_WHATIF_EDGE_UP);
   }
   __device__ __forceinline__ bool drained(uint32_t v) const {
     return ld_state<true>(nflags + v) & OGS_NODE_OVERLOADED;
@@ -209,7 +226,9 @@ struct WhatifRows {
     const uint32_t words = (E + 31u) / 32u;
     uint64_t* row = a.bits + size_t(u0) * a.ew;
     uint32_t* row32 = reinterpret_cast<uint32_t*>(row);
-    const bool metrics = m.metric_off && !u.hop;  // ignored under OGS_F_HOP_METRIC
+    // ignored under OGS_F_HOP_METRIC, but for the up flags of OGS_F_RESTORE
+    const bool restore = a.restore;
+    const bool metrics = m.metric_off && (!u.hop || restore);
     const uint32_t m0 = metrics ? m.metric_off[u0] : 0u;
     uint32_t mn = metrics ? m.metric_off[u0 + 1] - m0 : 0u;
     const bool tooLong = mn > m.max_metric_per_unit;
@@ -248,20 +267,32 @@ struct WhatifRows {
     for (uint32_t i = tid; i < mn; i += kGBlock) {
       const uint32_t e = m.metric_edges[m0 + i], v = m.metric_vals[m0 + i];
       if (e >= E) continue;  // skipped: sets no bit, so the search never returns it
-      if (v - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
+      const bool up = restore && (v & OGS_WHATIF_EDGE_UP);
+      const uint32_t nw = restore ? v & ~OGS_WHATIF_EDGE_UP : v;
+      if (u.hop) {  // weights ignored: only a revival counts
+        if (!up) continue;
+      } else if (nw - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
         wf[0] = 1u;
         continue;
       }
       atomicOr(&row32[2u * (e >> 5) + 1u], 1u << (e & 31u));
       if (!exits) continue;
       const uint64_t x = u.edges[e];
-      if (static_cast<uint32_t>(x) & OGS_EDGE_DOWN) continue;
+      if (static_cast<uint32_t>(x) & OGS_EDGE_DOWN) {
+        if (up) wf[1] = 1u;  // a revival: no exit-only path
+        continue;
+      }
+      if (u.hop) continue;
       const uint32_t w = static_cast<uint32_t>(x >> 32);
-      if (v < w || (v > w && tight(e, x))) wf[1] = 1u;
+      if (nw < w || (nw > w && tight(e, x))) wf[1] = 1u;
     }
     for (uint32_t i = r0 + tid; i < r1; i += kGBlock) {
       const uint32_t x = m.node_ids[i];
-      if (x < u.N) frow[x] = u.nflags[x] | m.node_bits[i];
+      if (x >= u.N) continue;
+      const uint8_t b = m.node_bits[i];
+      // OGS_F_RESTORE: clear-then-set (units with node lists take no exit)
+      frow[x] = restore ? uint8_t((u.nflags[x] & ~((b >> OGS_NODE_CLEAR_SHIFT) & 0x7u)) | (b & 0x0Fu))
+                        : uint8_t(u.nflags[x] | b);
     }
     round_sync<true>();
     const bool refused = wf[0] != 0u;
@@ -623,13 +654,13 @@ __global__ __launch_bounds__(kGBlock) void spf_global_kernel(
     for (uint32_t j = tid; j < m && j < 32u * uint32_t(st.words()); j += kGBlock) {
       const uint64_t x = u.edges[b + j];
       const uint32_t lo = static_cast<uint32_t>(x);
-      if (lo & OGS_EDGE_DOWN) continue;
       const uint32_t t = edge_dst(lo);
       D w0;
       if constexpr (M::kOn) {
-        if (mu.has(b + j)) continue;
+        if (mu.down(b + j, lo, mu.word((b + j) >> 5))) continue;
         w0 = u.hop ? D(1) : D(mu.weight(b + j, x));
       } else {
+        if (lo & OGS_EDGE_DOWN) continue;
         w0 = u.weight(x);
       }
       if (w0 == st.ld_dist(t)) {
@@ -784,14 +815,16 @@ __global__ __launch_bounds__(kGBlock) void spf_global_lds3_kernel(
 #pragma unroll
         for (int k = 0; k < kGRow; ++k) {
           const uint32_t lo = static_cast<uint32_t>(x[k]);
-          if (lo & OGS_EDGE_DOWN) continue;
           const uint32_t t = edge_dst(lo);
           uint32_t wk = hop ? 1u : static_cast<uint32_t>(x[k] >> 32);
           if constexpr (M::kOn) {
+            if (j0 + k >= m) continue;  // past the row: no bit is this edge's
             const uint32_t e = b + j0 + k, bit = 1u << (e & 31u);
             const uint64_t bw = (e >> 5) == ((b + j0) >> 5) ? b0 : b1;
-            if (static_cast<uint32_t>(bw) & bit) continue;  // dead in this unit
-            if (static_cast<uint32_t>(bw >> 32) & bit) wk = mu.search(e);
+            if (mu.down(e, lo, bw)) continue;  // dead, or down and not revived
+            if (!hop && (static_cast<uint32_t>(bw >> 32) & bit)) wk = M::weight_of(mu.search(e));
+          } else {
+            if (lo & OGS_EDGE_DOWN) continue;
           }
           const uint32_t c = dv + wk;
           // the source contributes its link slot, every other node NH(v)
@@ -1040,6 +1073,7 @@ hipError_t launch_whatif_global_w(const ogs_graph& g, const ogs_prefix_table& pt
   a.skip = skip;
   a.ew = ew;
   a.SnB = SnB;
+  a.restore = (flags & OGS_F_RESTORE) != 0;
   auto run = [&](auto k, uint32_t ldsBytes) {
     return launch_dyn_lds(k, dim3(nUnits), dim3(kGBlock), ldsBytes, stream, g, units, flags, W,
                           dist, nh, scratch, a);

@@ -67,7 +67,9 @@
     }
     me = after;
     mv = me + mods.max_metric_per_unit;
-    if (mods.metric_off && !hop) {  // under OGS_F_HOP_METRIC the metric lists are ignored
+    // under OGS_F_HOP_METRIC the metric lists are ignored, but for the up flags
+    // of OGS_F_RESTORE
+    if (mods.metric_off && (!hop || (flags & OGS_F_RESTORE))) {
       m0 = mods.metric_off[u0];
       mn = mods.metric_off[u0 + 1] - m0;
     }
@@ -158,16 +160,27 @@
       me[i] = e;
       mv[i] = v;
       if (e >= E) continue;  // skipped: sets no bit, so the search never returns it
-      if (v - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
+      const bool restore = (flags & OGS_F_RESTORE) != 0;
+      const bool up = restore && (v & OGS_WHATIF_EDGE_UP);
+      const uint32_t nw = restore ? v & ~OGS_WHATIF_EDGE_UP : v;
+      if (hop) {  // weights ignored: only a revival counts
+        if (!up) continue;
+      } else if (nw - 1u >= 0x7FFFFFFFu) {  // 0 or >= 2^31: the exact domain's
         wf[0] = 1u;
         continue;
       }
       atomicOr(&deadBits[2u * (e >> 5) + 1u], 1u << (e & 31u));
       const uint64_t x = edges[e];
-      if (static_cast<uint32_t>(x) & OGS_EDGE_DOWN) continue;
+      if (static_cast<uint32_t>(x) & OGS_EDGE_DOWN) {
+        // revived: nodes outside every base descendant set may get shorter
+        // paths, as for a lowered metric
+        if (up) wf[1] = 1u;
+        continue;
+      }
+      if (hop) continue;
       const uint32_t w = static_cast<uint32_t>(x >> 32);
-      if (v > w) seedOf(e);
-      else if (v < w) wf[1] = 1u;
+      if (nw > w) seedOf(e);
+      else if (nw < w) wf[1] = 1u;
     }
     }
     // a drained node's strict descendants: heads of its base-tight out-edges
@@ -177,8 +190,21 @@
       if (x >= N) continue;
       const uint8_t fx = gflags[x];
       uint8_t add = uint8_t(OGS_NODE_OVERLOADED);
-      if constexpr (WHATIF) add = mods.node_bits[i];
-      lflags[x] = fx | add;
+      if constexpr (WHATIF) {
+        add = mods.node_bits[i];
+        if (flags & OGS_F_RESTORE) {  // clear-then-set
+          const uint8_t clr = uint8_t((add >> OGS_NODE_CLEAR_SHIFT) & 0x7u);
+          add &= 0x0Fu;
+          // an undrained node transits again: shorter paths anywhere, as for
+          // a lowered metric (cleared soft-drain bits are selection only)
+          if ((fx & clr & ~add) & OGS_NODE_OVERLOADED) wf[1] = 1u;
+          lflags[x] = uint8_t(fx & ~clr) | add;
+        } else {
+          lflags[x] = fx | add;
+        }
+      } else {
+        lflags[x] = fx | add;
+      }
       if (!(add & OGS_NODE_OVERLOADED)) continue;  // soft-drain bits: selection only
       const uint32_t dx = bD[x];
       if (x == s || (fx & OGS_NODE_OVERLOADED) || dx == kInf) continue;

@@ -2175,8 +2175,9 @@ PYBIND11_MODULE(_decision, m) {
   // What-if sweep over Python-built LinkState / PrefixState objects (kept
   // alive by the sweep). A scenario is {"links": [(node, ifName), ...],
   // "nodesDown": [...], "nodesDrained": [...], "linkMetrics": [(node, ifName,
-  // metric), ...], "nodesSoftDrained": [(node, increment), ...]}, every key
-  // optional.
+  // metric), ...], "nodesSoftDrained": [(node, increment), ...],
+  // "linksUndrained": [(node, ifName), ...], "nodesUndrained": [...],
+  // "nodesSoftUndrained": [...]}, every key optional.
   auto toScenario = [](const py::dict& d) {
     LinkFailureSweep::Scenario s;
     if (d.contains("linkMetrics")) {
@@ -2199,6 +2200,18 @@ PYBIND11_MODULE(_decision, m) {
     if (d.contains("nodesDown")) s.nodesDown = d["nodesDown"].cast<std::vector<std::string>>();
     if (d.contains("nodesDrained")) {
       s.nodesDrained = d["nodesDrained"].cast<std::vector<std::string>>();
+    }
+    if (d.contains("linksUndrained")) {
+      for (const auto& l :
+           d["linksUndrained"].cast<std::vector<std::pair<std::string, std::string>>>()) {
+        s.linksUndrained.push_back({l.first, l.second});
+      }
+    }
+    if (d.contains("nodesUndrained")) {
+      s.nodesUndrained = d["nodesUndrained"].cast<std::vector<std::string>>();
+    }
+    if (d.contains("nodesSoftUndrained")) {
+      s.nodesSoftUndrained = d["nodesSoftUndrained"].cast<std::vector<std::string>>();
     }
     return s;
   };
@@ -2224,7 +2237,9 @@ PYBIND11_MODULE(_decision, m) {
         py::arg("linkState"), py::arg("me"), py::arg("scenario"));
   // every list of the expansion: {"dead": [(node, other, ifName)], "drained":
   // [node], "metrics": [(node, other, ifName, weight)] in edge-id order,
-  // "metricEdges": [edge id], "flags": [(node, bits)]}
+  // "metricEdges": [edge id], "flags": [(node, bits)], "revived": [(node,
+  // other, ifName, weight)] in edge-id order, "revivedEdges": [edge id],
+  // "cleared": [(node, bits)]}
   m.def("expand_whatif",
         [toScenario](const LinkState& ls, const std::string& me, const py::dict& sc) {
           const auto x = LinkFailureSweep::expandScenario(ls, me, toScenario(sc));
@@ -2252,12 +2267,24 @@ PYBIND11_MODULE(_decision, m) {
           for (size_t i = 0; i < x.flagNodes.size(); ++i) {
             flags.emplace_back(f.names[x.flagNodes[i]], int(x.flagBits[i]));
           }
+          std::vector<std::tuple<std::string, std::string, std::string, uint64_t>> revived;
+          for (size_t i = 0; i < x.revivedEdges.size(); ++i) {
+            revived.push_back(std::tuple_cat(edge(x.revivedEdges[i]),
+                                             std::make_tuple(x.revivedVals[i])));
+          }
+          std::vector<std::pair<std::string, int>> cleared;
+          for (size_t i = 0; i < x.clearedNodes.size(); ++i) {
+            cleared.emplace_back(f.names[x.clearedNodes[i]], int(x.clearedBits[i]));
+          }
           py::dict out;
           out["dead"] = dead;
           out["drained"] = drained;
           out["metrics"] = metrics;
           out["metricEdges"] = x.metricEdges;
           out["flags"] = flags;
+          out["revived"] = revived;
+          out["revivedEdges"] = x.revivedEdges;
+          out["cleared"] = cleared;
           return out;
         },
         py::arg("linkState"), py::arg("me"), py::arg("scenario"));

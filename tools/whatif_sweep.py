@@ -28,8 +28,25 @@ each row also giving the share of exit-only units (no node bit, no lowered
 metric, no dead or raised edge tight in the base SPF: computed here on the
 host from the base SPF, the rule the kernel applies).
 
+With --restore the world carries a drained baseline -- every other node
+hard-drained, every 20th link overloaded at one end, every other node (the
+other half) soft-drained by 1000 -- and the sets put things back, one scenario
+per restoration (--drain-every N: every Nth node instead of every other one;
+with every other node hard-drained the source reaches few nodes, so most
+restorations move few routes):
+  (m) each drained node undrained,  (n) each overloaded link brought up,
+  (o) each soft-drained node soft-undrained,
+  (s) a sample of 64 from (m) and (o),
+in mode kChangedOnly; (n) and (s) also in kFull beside it: link revivals run
+there in the full frontier form, and cleared node bits are not built in that
+form, so (s) runs as topology copies -- the kernels every sweep had before
+restorations. With --g1 --restore the first three on the G1 WAN, 2,000
+scenarios each, as (p), (q), (r) in the global-state form (restoring units take
+no exit).
+
   python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg]
-  python tools/whatif_sweep.py --g1 [--nodes 20000] [--sample 64] [--sets hijkl]"""
+  python tools/whatif_sweep.py --g1 [--nodes 20000] [--sample 64] [--sets hijkl]
+  python tools/whatif_sweep.py --restore [--g1] [--sets mnos | pqr]"""
 import argparse
 import hashlib
 import json
@@ -70,14 +87,25 @@ def main():
     ap.add_argument("--sample", type=int, default=64)
     ap.add_argument("--sets", default=None, help="the sets to run, by letter")
     ap.add_argument("--g1", action="store_true", help="the G1 WAN and its sets (h .. l)")
+    ap.add_argument("--restore", action="store_true",
+                    help="the drained baseline and its restoring sets (m .. o and s, with --g1 p .. r)")
+    ap.add_argument("--drain-every", type=int, default=2,
+                    help="the baseline drains every Nth node hard and every Nth (the next one) "
+                         "soft; 2 (default): every other node each")
     args = ap.parse_args()
     if args.sets is None:
-        args.sets = "hijkl" if args.g1 else "abcdefg"
+        if args.restore:
+            args.sets = "pqr" if args.g1 else "mnos"
+        else:
+            args.sets = "hijkl" if args.g1 else "abcdefg"
+    if args.restore != all(c in "mnopqrs" for c in args.sets):
+        ap.error("sets m .. s run on the drained baseline (--restore), the others without it")
     import torch  # noqa: F401  (one HIP runtime: torch's)
     import _refcpu as O
     import openr_amd
     import whatif as W
     import whatif_metric as WM
+    import whatif_restore as WR
     from openr_amd.workloads import (C4_DUAL_PERMILLE, C4_OPTS, C4_SEED, C4_SOURCE,
                                      C4_VARIANTS)
     openr_amd.require_gpu()
@@ -87,12 +115,23 @@ def main():
     if args.nodes:
         opts["nodes"] = args.nodes
     me = C4_SOURCE
-    w = WM.as_metric_world(W.generated_world(M, "wan", opts))
+    w = WR.as_restore_world(W.generated_world(M, "wan", opts))
     if args.g1:
-        w = fresh_world(WM.MetricWorld)(list(w.adjdbs.values()), w.prefix_dbs, w.area)
+        w = fresh_world(WR.RestoreWorld)(list(w.adjdbs.values()), w.prefix_dbs, w.area)
     names = sorted(n for n in w.adjdbs if n != me)
     links = sorted({min((n, a["ifName"]), (a["otherNodeName"], a["otherIfName"]))
                     for n, d in w.adjdbs.items() for a in d["adjacencies"]})
+    step = max(2, args.drain_every)
+    hard, over, softs = names[::step], links[::20], names[1::step]
+    if args.restore:  # the drained baseline
+        for n in hard:
+            w.adjdbs[n]["isOverloaded"] = True
+        for n, i in over:
+            next(a for a in w.adjdbs[n]["adjacencies"] if a["ifName"] == i)["isOverloaded"] = True
+        for n in softs:
+            w.adjdbs[n]["nodeMetricIncrementVal"] = 1000
+            for a in w.adjdbs[n]["adjacencies"]:
+                a["metric"] += 1000
     rng = random.Random(0xC4F)
 
     def both(n, ifn, metric):  # the link behind (n, ifn): both directions sent with `metric`
@@ -126,6 +165,17 @@ def main():
         ("l: every 20th link to 1", [{"linkMetrics": both(n, i, lambda x: 1)}
                                      for n, i in links[::20]], False, (2,)),
     ]
+    sets += [
+        ("m: node undrained", [{"nodesUndrained": [n]} for n in hard], False, (2,)),
+        ("n: link brought up", [{"linksUndrained": [l]} for l in over], False, (2, 0)),
+        ("o: node soft-undrained", [{"nodesSoftUndrained": [n]} for n in softs], False, (2,)),
+        ("s: sample of m and o", [{"nodesUndrained": [n]} for n in every(hard, 32)] +
+         [{"nodesSoftUndrained": [n]} for n in every(softs, 32)], False, (2, 0)),
+        ("p: node undrained", [{"nodesUndrained": [n]} for n in every(hard, 2000)], False, (2,)),
+        ("q: link brought up", [{"linksUndrained": [l]} for l in every(over, 2000)], False, (2,)),
+        ("r: node soft-undrained", [{"nodesSoftUndrained": [n]} for n in every(softs, 2000)],
+         False, (2,)),
+    ]
     sets = [s for s in sets if s[0][0] in args.sets]
     print(f"what-if sweep, {'G1' if args.g1 else 'C4'} WAN: {len(w.adjdbs)} nodes, "
           f"{w.directed_edges()} directed edges, "
@@ -145,6 +195,8 @@ def main():
         """the kernel's rule for a unit that runs nothing, from the base SPF
         (the G1 sets' scenario kinds; the world has no link down)"""
         if sc.get("nodesDrained") or sc.get("nodesSoftDrained"):
+            return False
+        if any(sc.get(k) for k in WR.RESTORING):  # a restoring unit takes no exit
             return False
 
         def tight(n, ifn):  # either direction of the link behind (n, ifn)
