@@ -73,7 +73,8 @@ ASAN_BIN := build/asan/host_asan
 ASAN_REF := build/asan/_refcpu$(EXT)
 ASAN_LOG ?= profiles/r06_asan.log
 ASAN_STUBS := tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp tests/asan/ogs_stub_scenarios.cpp \
-  tests/asan/ogs_stub_whatif.cpp tests/asan/ogs_stub_whatif_global.cpp
+  tests/asan/ogs_stub_whatif.cpp tests/asan/ogs_stub_whatif_global.cpp \
+  tests/asan/ogs_stub_node_diff.cpp
 $(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp $(ASAN_STUBS)
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \

@@ -57,8 +57,11 @@ extern "C" {
  * 8: ogs_route_delta. Still 8, additive: libraries from the what-if
  * scenario sweep on also export ogs_spf_routes_scenarios /
  * ogs_ctx_spf_routes_scenarios, and from the metric / soft-drain sweep on
- * ogs_spf_routes_whatif / ogs_ctx_spf_routes_whatif; a consumer that may
- * meet an older ABI-8 library detects them by symbol (dlsym). */
+ * ogs_spf_routes_whatif / ogs_ctx_spf_routes_whatif, and from the node-label
+ * sweep on ogs_spf_node_diff / ogs_spf_node_changes_gather (the "ABI 9"
+ * additions: the number stays 8 because they change no existing entry); a
+ * consumer that may meet an older ABI-8 library detects them by symbol
+ * (dlsym). */
 #define OGS_ABI_VERSION 8
 
 /* ---- status codes ------------------------------------------------------ */
@@ -770,6 +773,69 @@ int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
                              int32_t max_prefixes, const ogs_spf_out* records,
                              int32_t nh_words, const ogs_route_changes* changes,
                              void* stream);
+
+/* SPF-row diff of n_units units against ONE base unit's rows (same topology
+ * and source): which nodes' {reached, distance, next-hop set} moved. A
+ * node-label MPLS route source -> owner v (SpfSolver.cpp:352-445) is a
+ * function of v's SPF row alone, so these are the owners whose label routes
+ * DecisionRouteDb::calculateUpdate (SpfSolver.cpp:41-54) may report. Node v of
+ * a unit is changed when its reachedness (distance != all-ones) differs from
+ * the base's, or both are reached and the distance or any next-hop word
+ * differs; two unreached rows are equal whatever their next-hop words hold.
+ * The unit's own source and nodes at or past the topology's node count are
+ * never reported. */
+typedef struct ogs_node_diff {
+  const uint32_t* base_dist;   /* [S_n] base unit's distances              */
+  const uint32_t* base_nh;     /* [W * S_n] and next-hop sets, word w of
+                                  node v at base_nh[w * S_n + v]           */
+  const uint32_t* interest;    /* optional [ceil(S_n/32)]: only nodes whose
+                                  bit is set are compared                  */
+  const uint32_t* unit_counts; /* optional [2 * n_units], the counts of the
+                                  ogs_route_diff that produced the rows: a
+                                  unit whose entry 2u is OGS_WHATIF_REFUSED
+                                  wrote no rows; it gets count 0 and a zero
+                                  bitmap and its rows are never read       */
+  uint32_t* changed;           /* [n_units * ceil(S_n/32)] bit v of unit u's
+                                  row: node v changed. Every word is written
+                                  by the call (no zeroing needed before)   */
+  uint32_t* counts;            /* [n_units] changed nodes of each unit     */
+} ogs_node_diff;
+
+/* One launch on `stream`, one workgroup per unit, no atomics; no workgroup
+ * waits on another. rows->dist [n_units * S_n] and rows->nh
+ * [(u * W + w) * S_n + v] in ogs_spf_out's layout with S_n = graph->max_nodes,
+ * 32-bit distances; graph->node_base and units (device) give each unit's node
+ * count and source. Rows are read 16 bytes at a time where every row start is
+ * 16-byte aligned (S_n a multiple of 4 and aligned pointers), else element by
+ * element. graph, units, rows, rows->dist / nh, diff or a required field of
+ * it NULL, n_units < 0: OGS_E_INVALID. OGS_F_WIDE_METRIC (64-bit distances),
+ * nh_words other than 1, 2 or 4, max_nodes outside (0, 2^21]:
+ * OGS_E_UNSUPPORTED. n_units == 0: OGS_OK. Additive to ABI 8 (detect by
+ * symbol); no ogs_ctx_ form: the call uses no engine scratch and no knob. */
+int ogs_spf_node_diff(const ogs_graph* graph, const ogs_unit* units /* device */,
+                      int32_t n_units, const ogs_spf_out* rows,
+                      const ogs_node_diff* diff, uint32_t flags, int32_t nh_words,
+                      void* stream);
+
+/* Compact list of the changed nodes' rows, unit-major, node id ascending
+ * within a unit (the ogs_route_changes layout for SPF rows). */
+typedef struct ogs_node_changes {
+  const uint32_t* offsets; /* [n_units + 1] exclusive scan of
+                              ogs_node_diff.counts; offsets[n_units] == total */
+  size_t total;            /* number of records (nh stride)              */
+  uint32_t* node;          /* [total] node id                            */
+  uint32_t* dist;          /* [total] the unit's distance to it          */
+  uint32_t* nh;            /* [nh_words * total] next-hop set, word w of
+                              record i at nh[w * total + i]              */
+} ogs_node_changes;
+
+/* Gathers the rows of the nodes marked in `changed` (ogs_node_diff.changed
+ * of the same units and rows) into `changes`. A unit never writes past its
+ * own slice of the record arrays. nh_words 1, 2 or 4. */
+int ogs_spf_node_changes_gather(const uint32_t* changed, int32_t n_units,
+                                int32_t max_nodes, const ogs_spf_out* rows,
+                                int32_t nh_words, const ogs_node_changes* changes,
+                                void* stream);
 
 /* Route delta of ONE source between two builds (ABI 8): what
  * Decision::rebuildRoutes' full branch (Decision.cpp:912-927) gets from

@@ -37,6 +37,7 @@ EXPORTS = [
     "ogs_spf_routes_scenarios", "ogs_ctx_spf_routes_scenarios",
     "ogs_spf_routes_whatif", "ogs_ctx_spf_routes_whatif",
     "ogs_spf_routes_whatif_global", "ogs_whatif_needs_global",
+    "ogs_spf_node_diff", "ogs_spf_node_changes_gather",
 ]
 
 OGS_WHATIF_REFUSED = 0xFFFFFFFF
@@ -113,6 +114,21 @@ class RouteDiff(ctypes.Structure):
                 ("base_desc", ctypes.c_void_p), ("base_desc_valid", ctypes.c_int32)]
 
 
+class NodeDiff(ctypes.Structure):
+    """ogs_node_diff: the base unit's SPF rows, optional interest mask and
+    unit counts, and the changed bitmap / counts the call writes."""
+    _fields_ = [("base_dist", ctypes.c_void_p), ("base_nh", ctypes.c_void_p),
+                ("interest", ctypes.c_void_p), ("unit_counts", ctypes.c_void_p),
+                ("changed", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+class NodeChanges(ctypes.Structure):
+    """ogs_node_changes: offsets, total and the compact record arrays."""
+    _fields_ = [("offsets", ctypes.c_void_p), ("total", ctypes.c_size_t),
+                ("node", ctypes.c_void_p), ("dist", ctypes.c_void_p),
+                ("nh", ctypes.c_void_p)]
+
+
 def route_delta_workspace_bytes(num_prefixes):
     """OGS_ROUTE_DELTA_WORKSPACE_BYTES of include/openr_gpu.h."""
     return (num_prefixes + OGS_ROUTE_DELTA_TILE - 1) // OGS_ROUTE_DELTA_TILE * 528
@@ -185,6 +201,14 @@ def load(path=None):
     lib.ogs_spf_routes_whatif_global.restype = ctypes.c_int
     lib.ogs_whatif_needs_global.argtypes = [ctypes.POINTER(Graph), U32, I32]
     lib.ogs_whatif_needs_global.restype = ctypes.c_int
+    # SPF-row diff and gather of the node-label sweep (no ogs_ctx_ twins)
+    lib.ogs_spf_node_diff.argtypes = [
+        ctypes.POINTER(Graph), P, I32, ctypes.POINTER(SpfOut), ctypes.POINTER(NodeDiff), U32,
+        I32, P]
+    lib.ogs_spf_node_diff.restype = ctypes.c_int
+    lib.ogs_spf_node_changes_gather.argtypes = [
+        P, I32, I32, ctypes.POINTER(SpfOut), I32, ctypes.POINTER(NodeChanges), P]
+    lib.ogs_spf_node_changes_gather.restype = ctypes.c_int
     return lib
 
 

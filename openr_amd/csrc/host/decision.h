@@ -1115,6 +1115,21 @@ bool wideDistancesNeeded(const FlatTopology& f);
 // label -> (owner node, route), the reference's labelToNode
 // (SpfSolver.cpp:356-358, duplicate labels: smallest owner name wins)
 using LabelRoutes = std::map<int32_t, std::pair<std::string, RibMplsEntry>>;
+// a node label the reference installs: nonzero, top 12 bits clear
+// (SpfSolver.cpp:360-368)
+inline bool validNodeLabel(int32_t label) {
+  return (static_cast<uint32_t>(label) & 0xfff00000u) == 0 && label != 0;
+}
+// One owner's candidate route for its node label (SpfSolver.cpp:376-437):
+// POP_AND_LOOKUP when the owner is `me`; else a next hop per link slot of the
+// owner's set (word w at nhWords[w * nhStride]; rb = the source's CSR row
+// start), PHP when the link ends at the owner, SWAP otherwise, metric = dist;
+// nullopt when the owner is unreached or its set is empty.
+std::optional<RibMplsEntry> nodeLabelEntry(const FlatTopology& f, const std::string& area,
+                                           const std::string& me, uint32_t rb,
+                                           const std::string& node, int32_t label, bool reached,
+                                           uint64_t dist, const uint32_t* nhWords,
+                                           size_t nhStride, int W);
 // Node-label routes of one area from the source's SPF there (dist/nh as in
 // UnitView; dist == nullptr when the source has no SPF in that area).
 void addNodeLabelRoutes(const LinkState& ls, const FlatTopology& f,
@@ -1202,8 +1217,14 @@ DecisionRouteDb materializeRouteDb(
 // (exact extraction order, 64-bit distances), in ogs_spf_routes launches of
 // up to kExactChunk (256) topologies each, rebuilt from the live `ls` / `ps`
 // at launch time, and diff on the host with calculateUpdate. Node-segment
-// labels are not part of the sweep (off in the DecisionBenchmark config,
-// SURVEY.md A.8). `ls` and `ps` must outlive the sweep unchanged.
+// labels (SpfSolver.cpp:352-445; off in the DecisionBenchmark config,
+// SURVEY.md A.8) join the sweep with enableNodeSegmentLabel: every launch then
+// also writes the scenarios' SPF rows, ogs_spf_node_diff marks the label
+// owners whose row left the base's, ogs_spf_node_changes_gather compacts
+// those rows, and the host re-resolves the labels they own into
+// mplsRoutesToUpdate / mplsRoutesToDelete. Without it a
+// sweep launches, allocates and returns what it did before the option
+// existed. `ls` and `ps` must outlive the sweep unchanged.
 class LinkFailureSweep {
  public:
   struct LinkDown {  // one end of the link: (node, its interface)
@@ -1213,7 +1234,7 @@ class LinkFailureSweep {
                    const PrefixState& ps,
                    const std::vector<std::vector<LinkDown>>& variants,
                    bool enableV4, bool enableBestRouteSelection = false,
-                   bool v4OverV6Nexthop = false);
+                   bool v4OverV6Nexthop = false, bool enableNodeSegmentLabel = false);
   // A what-if scenario of any size; what each kind stands for in the reference:
   //  linksDown     the adjacency removed at both ends (LinkState.cpp:491-634);
   //                a shared-risk group names all its links
@@ -1304,7 +1325,7 @@ class LinkFailureSweep {
   LinkFailureSweep(const std::string& myNodeName, const LinkState& ls,
                    const PrefixState& ps, const std::vector<Scenario>& scenarios,
                    bool enableV4, bool enableBestRouteSelection = false,
-                   bool v4OverV6Nexthop = false);
+                   bool v4OverV6Nexthop = false, bool enableNodeSegmentLabel = false);
   // How a launch holds "what is removed": kRegisterList every scenario has at
   // most 8 dead directed edges and no drain (ogs_spf_routes_variants);
   // kEdgeBitset ogs_spf_routes_scenarios (LDS bitset, drained-flag row), or
@@ -1366,6 +1387,13 @@ class LinkFailureSweep {
   DecisionRouteDb routeDb(size_t v) const;                // after fetchRecords
   std::vector<std::string> changedPrefixes(size_t v) const;  // after either
   std::pair<uint32_t, uint32_t> counts(size_t v) const;   // {update, delete}
+  // node-label routes of variant v (enableNodeSegmentLabel; {0, 0} / empty
+  // without): {mplsRoutesToUpdate, mplsRoutesToDelete} sizes and the labels of
+  // both, ascending. counts / changedPrefixes / totalChanges stay unicast-only
+  std::pair<uint32_t, uint32_t> mplsCounts(size_t v) const;  // after either fetch
+  std::vector<int32_t> changedLabels(size_t v) const;
+  uint64_t totalChangedNodes() const { return nodeOffsets_.empty() ? 0 : nodeOffsets_.back(); }
+  bool nodeSegmentLabels() const { return labels_; }
   uint64_t totalChanges() const { return offsets_.empty() ? 0 : offsets_.back(); }
   int nhWords() const { return W_; }
   const HostBatch& batch() const { return hb_; }
@@ -1386,6 +1414,26 @@ class LinkFailureSweep {
   const PrefixState& ps_;
   std::string me_, area_;
   bool enableV4_, brs_, v4OverV6_;
+  // node-label routes (enableNodeSegmentLabel): nodeLabel_[v] = node v's label
+  // when valid, else 0; labelOwners_[label] = its owners, node name ascending;
+  // dInterest_ = the bitmap of labelled nodes (ogs_node_diff.interest)
+  bool labels_{false};
+  std::vector<int32_t> nodeLabel_;
+  std::map<int32_t, std::vector<uint32_t>> labelOwners_;
+  DeviceBuffer dInterest_, dNodeChanged_, dNodeCounts_, dNodeOffsets_, cNode_, cNodeDist_, cNodeNh_;
+  size_t nodeWords_{1};
+  // fetched: base rows, per-variant counts / offsets / compact changed rows
+  // (fetchUpdates) or full rows (fetchRecords)
+  std::vector<uint32_t> baseDist_, baseNh_, nodeCounts_, nodeOffsets_;
+  std::vector<uint32_t> cNodeH_, cNodeDistH_, cNodeNhH_, dist_, nh_;
+  void runNodeDiff(const ogs_graph& g, void* stream);
+  void addBaseLabelRoutes(DecisionRouteDb& db) const;
+  // variant v's label changes against baseRouteDb() into u (fetchUpdates)
+  void addMplsUpdate(size_t v, DecisionRouteUpdate& u) const;
+  DecisionRouteUpdate mplsUpdate(size_t v) const;  // after either fetch
+  // copies form: every topology's SPF rows (64-bit distances, settled bits)
+  std::vector<uint64_t> xDist_;
+  std::vector<uint32_t> xNh_, xReach_;
   PrefixHostTable table_;
   HostBatch hb_;
   int W_{1};

@@ -69,9 +69,9 @@ std::vector<LinkFailureSweep::Scenario> linkScenarios(
 LinkFailureSweep::LinkFailureSweep(
     const std::string& myNodeName, const LinkState& ls, const PrefixState& ps,
     const std::vector<std::vector<LinkDown>>& variants, bool enableV4,
-    bool enableBestRouteSelection, bool v4OverV6Nexthop)
+    bool enableBestRouteSelection, bool v4OverV6Nexthop, bool enableNodeSegmentLabel)
     : LinkFailureSweep(myNodeName, ls, ps, linkScenarios(variants), enableV4,
-                       enableBestRouteSelection, v4OverV6Nexthop) {}
+                       enableBestRouteSelection, v4OverV6Nexthop, enableNodeSegmentLabel) {}
 
 LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
                                                             const std::string& me,
@@ -314,6 +314,8 @@ void LinkFailureSweep::reselect() {
   xUpd_.clear();
   base_.reset();
   baseMeta_.clear();
+  nodeOffsets_.clear();
+  dist_.clear();
 }
 
 void LinkFailureSweep::setListForm(bool forceBitset) {
@@ -414,14 +416,15 @@ void LinkFailureSweep::globalLaunch(const ogs_graph& g, const ogs_prefix_table& 
 LinkFailureSweep::LinkFailureSweep(
     const std::string& myNodeName, const LinkState& ls, const PrefixState& ps,
     const std::vector<Scenario>& scenarios, bool enableV4,
-    bool enableBestRouteSelection, bool v4OverV6Nexthop)
+    bool enableBestRouteSelection, bool v4OverV6Nexthop, bool enableNodeSegmentLabel)
     : ls_(ls),
       ps_(ps),
       me_(myNodeName),
       area_(ls.getArea()),
       enableV4_(enableV4),
       brs_(enableBestRouteSelection),
-      v4OverV6_(v4OverV6Nexthop) {
+      v4OverV6_(v4OverV6Nexthop),
+      labels_(enableNodeSegmentLabel) {
   const FlatTopology& f = ls.flat();
   auto sIt = f.id.find(me_);
   if (sIt == f.id.end()) {
@@ -530,6 +533,22 @@ LinkFailureSweep::LinkFailureSweep(
   dMask_.resize(Uc * W_ * Sp_ * 4);
   dChanged_.resize(Uc * words_ * 4);
   dCounts_.resize(Uc * 2 * 4);
+  if (labels_) {
+    // the label owners: who is compared on the device, who competes per label
+    nodeWords_ = (Sn + 31) / 32;
+    nodeLabel_.assign(f.names.size(), 0);
+    std::vector<uint32_t> interest(nodeWords_, 0u);
+    for (const auto& [node, adjDb] : ls.getAdjacencyDatabases()) {  // node name ascending
+      const auto it = f.id.find(node);
+      if (it == f.id.end() || !validNodeLabel(adjDb.nodeLabel)) continue;
+      nodeLabel_[it->second] = adjDb.nodeLabel;
+      labelOwners_[adjDb.nodeLabel].push_back(it->second);
+      interest[it->second >> 5] |= 1u << (it->second & 31u);
+    }
+    dInterest_.upload(interest.data(), interest.size());
+    dNodeChanged_.resize(Uc * nodeWords_ * 4);
+    dNodeCounts_.resize(Uc * 4);
+  }
 }
 
 // Variants outside the repair kernel's domain: ogs_spf_routes launches over
@@ -548,8 +567,15 @@ void LinkFailureSweep::exactLaunch(void* stream) {
   xMeta_.assign(T * Sp_, 0);
   xMetric_.assign(T * Sp_, 0);
   xMask_.assign(T * W_ * Sp_, 0);
+  // label routes come from each copy's SPF rows: fetched with the records
+  const size_t Sn = size_t(std::max(hb_.maxNodes, 1)), rw = (Sn + 31) / 32;
+  if (labels_) {
+    xDist_.assign(T * Sn, 0);
+    xNh_.assign(T * W_ * Sn, 0);
+    xReach_.assign(exactOrder_ ? T * rw : 0, 0);
+  }
   HostBatchImage img;  // reused (grow-only) by every chunk
-  DeviceBuffer units, meta, metric, mask;
+  DeviceBuffer units, meta, metric, mask, dist, nh, reach;
   for (size_t c0 = 0; c0 < T; c0 += kExactChunk) {
     const size_t c1 = std::min(T, c0 + kExactChunk), n = c1 - c0;
     HostBatch hb;  // topology t - c0 = the base (t = 0) or variant t - 1
@@ -615,8 +641,23 @@ void LinkFailureSweep::exactLaunch(void* stream) {
     const ogs_prefix_table pt = img.table(hb);
     ogs_spf_out out{nullptr, nullptr, meta.as<uint32_t>(), metric.get(), mask.as<uint32_t>(),
                     nullptr};
+    if (labels_) {
+      dist.resize(n * Sn * 8);
+      nh.resize(n * W_ * Sn * 4);
+      out.dist = dist.get();
+      out.nh = nh.as<uint32_t>();
+      if (exactOrder_) {
+        reach.resize(n * rw * 4);
+        out.reached = reach.as<uint32_t>();
+      }
+    }
     ogsCheck(ogs_spf_routes(&g, &pt, units.as<ogs_unit>(), int32_t(n), fl, W_, &out, stream),
              "ogs_spf_routes(variant topologies)");
+    if (labels_) {
+      dist.download(xDist_.data() + c0 * Sn, n * Sn, stream);
+      nh.download(xNh_.data() + c0 * W_ * Sn, n * W_ * Sn, stream);
+      if (exactOrder_) reach.download(xReach_.data() + c0 * rw, n * rw, stream);
+    }
     meta.download(xMeta_.data() + c0 * Sp_, n * Sp_, stream);
     metric.download(xMetric_.data() + c0 * Sp_, n * Sp_, stream);
     // mask rows [(i * W + w) * Sp + p] of the chunk follow the previous ones
@@ -641,6 +682,13 @@ void LinkFailureSweep::exactFetch(void* /*stream*/) {
                                 &mask[t * W_ * Sp_ + p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE,
                                 OGS_POLICY_NONE);
       if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
+    }
+    if (labels_) {  // the copy's own rows through the solver's label pass
+      const size_t Sn = size_t(std::max(hb_.maxNodes, 1)), rw = (Sn + 31) / 32;
+      LabelRoutes labelToNode;
+      addNodeLabelRoutes(ls_, f, area_, me_, &xDist_[t * Sn], &xNh_[t * W_ * Sn], Sn, W_,
+                         labelToNode, exactOrder_ ? &xReach_[t * rw] : nullptr);
+      for (auto& [label, ne] : labelToNode) db.mplsRoutes.emplace(label, std::move(ne.second));
     }
     return db;
   };
@@ -682,6 +730,8 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   changed_.clear();
   meta_.clear();
   counts_.clear();
+  nodeOffsets_.clear();
+  dist_.clear();
   const ogs_graph g = img_.graph(hb_, 1);
   const ogs_prefix_table pt = img_.table(hb_);
   const bool changedOnly = mode_ == kChangedOnly && W_ == 1;
@@ -690,6 +740,10 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     out = ogs_spf_out{dDist_.get(), dNh_.as<uint32_t>(), dMeta_.as<uint32_t>(),
                       dMetric_.get(), dMask_.as<uint32_t>(), dSel_.as<uint32_t>()};
     if (changedOnly) out.dist = out.nh = nullptr;  // records of changed routes only
+  }
+  if (labels_) {  // the label routes are read off every scenario's SPF rows
+    out.dist = dDist_.get();
+    out.nh = dNh_.as<uint32_t>();
   }
   // the base's tight-DAG descendant rows: built by the first repair launch
   // after runBase, reused by the next ones (same topology, source, base SPF)
@@ -751,8 +805,22 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     ogsCheck(rc, "ogs_spf_routes_scenarios");
   }
   descValid_ = diff.base_desc_valid != 0;  // set by the library when it wrote the rows
+  if (labels_) runNodeDiff(g, stream);
   recordsRun_ = records;
   changedOnlyRun_ = records && changedOnly;
+}
+
+// The label owners whose SPF row left the base's, over every scenario's rows
+// (whichever form wrote them; a refused unit wrote none and reports none).
+void LinkFailureSweep::runNodeDiff(const ogs_graph& g, void* stream) {
+  nodeOffsets_.clear();
+  const ogs_spf_out rows{dDist_.get(), dNh_.as<uint32_t>()};
+  const ogs_node_diff nd{bDist_.as<uint32_t>(),        bNh_.as<uint32_t>(),
+                         dInterest_.as<uint32_t>(),    dCounts_.as<uint32_t>(),
+                         dNodeChanged_.as<uint32_t>(), dNodeCounts_.as<uint32_t>()};
+  ogsCheck(ogs_spf_node_diff(&g, dUnits_.as<ogs_unit>(), int32_t(numVariants()), &rows, &nd, 0u,
+                             W_, stream),
+           "ogs_spf_node_diff");
 }
 
 void LinkFailureSweep::fetchUpdates(void* stream) {
@@ -763,6 +831,10 @@ void LinkFailureSweep::fetchUpdates(void* stream) {
   const size_t U = numVariants();
   counts_.resize(U * 2);
   if (U) dCounts_.download(counts_.data(), U * 2, stream);
+  if (labels_) {
+    nodeCounts_.resize(U);
+    if (U) dNodeCounts_.download(nodeCounts_.data(), U, stream);
+  }
   ogsCheck(ogs_stream_sync(stream), "ogs_stream_sync");
   offsets_.assign(U + 1, 0);
   uint64_t total = 0;
@@ -796,6 +868,41 @@ void LinkFailureSweep::fetchUpdates(void* stream) {
     cMetric_.download(cMetricH_.data(), total, stream);
     cMask_.download(cMaskH_.data(), total * W_, stream);
   }
+  if (labels_) {  // the same for the changed SPF rows
+    const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
+    nodeOffsets_.assign(U + 1, 0);
+    uint64_t nodes = 0;
+    for (size_t v = 0; v < U; ++v) {
+      nodeOffsets_[v] = uint32_t(nodes);
+      nodes += nodeCounts_[v];
+      if (nodes > 0xFFFFFFFFull) throw std::length_error("LinkFailureSweep: > 2^32 changes");
+    }
+    nodeOffsets_[U] = uint32_t(nodes);
+    const size_t Tn = std::max<size_t>(nodes, 1);
+    dNodeOffsets_.upload(nodeOffsets_.data(), nodeOffsets_.size(), stream);
+    cNode_.resize(Tn * 4);
+    cNodeDist_.resize(Tn * 4);
+    cNodeNh_.resize(Tn * W_ * 4);
+    const ogs_spf_out rows{dDist_.get(), dNh_.as<uint32_t>()};
+    const ogs_node_changes nc{dNodeOffsets_.as<uint32_t>(), size_t(nodes), cNode_.as<uint32_t>(),
+                              cNodeDist_.as<uint32_t>(), cNodeNh_.as<uint32_t>()};
+    ogsCheck(ogs_spf_node_changes_gather(dNodeChanged_.as<uint32_t>(), int32_t(U), int32_t(Sn),
+                                         &rows, W_, &nc, stream),
+             "ogs_spf_node_changes_gather");
+    cNodeH_.resize(nodes);
+    cNodeDistH_.resize(nodes);
+    cNodeNhH_.resize(nodes * W_);
+    if (nodes) {
+      cNode_.download(cNodeH_.data(), nodes, stream);
+      cNodeDist_.download(cNodeDistH_.data(), nodes, stream);
+      cNodeNh_.download(cNodeNhH_.data(), nodes * W_, stream);
+    }
+    baseDist_.resize(Sn);
+    baseNh_.resize(W_ * Sn);
+    bDist_.download(baseDist_.data(), Sn, stream);
+    bNh_.download(baseNh_.data(), W_ * Sn, stream);
+    dist_.clear();
+  }
   baseMeta_.resize(Sp_);
   baseMetric_.resize(Sp_);
   baseMask_.resize(W_ * Sp_);
@@ -825,6 +932,19 @@ void LinkFailureSweep::fetchRecords(void* stream) {
     dMetric_.download(metric_.data(), U * Sp_, stream);
     dMask_.download(mask_.data(), U * W_ * Sp_, stream);
   }
+  if (labels_) {  // every scenario's SPF rows: the launch always writes them
+    const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
+    dist_.resize(U * Sn);
+    nh_.resize(U * W_ * Sn);
+    if (U) {
+      dDist_.download(dist_.data(), U * Sn, stream);
+      dNh_.download(nh_.data(), U * W_ * Sn, stream);
+    }
+    baseDist_.resize(Sn);
+    baseNh_.resize(W_ * Sn);
+    bDist_.download(baseDist_.data(), Sn, stream);
+    bNh_.download(baseNh_.data(), W_ * Sn, stream);
+  }
   baseMeta_.resize(Sp_);
   baseMetric_.resize(Sp_);
   baseMask_.resize(W_ * Sp_);
@@ -849,9 +969,114 @@ const DecisionRouteDb& LinkFailureSweep::baseRouteDb() const {
                                 &baseMask_[p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE, OGS_POLICY_NONE);
       if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
     }
+    if (labels_) addBaseLabelRoutes(db);
     base_ = std::move(db);
   }
   return *base_;
+}
+
+namespace {
+
+// 32-bit SPF rows as addNodeLabelRoutes reads them (all-ones = unreachable)
+std::vector<uint64_t> widenDist(const uint32_t* d, size_t n) {
+  std::vector<uint64_t> out(n);
+  for (size_t i = 0; i < n; ++i) out[i] = d[i] == 0xFFFFFFFFu ? ~0ull : d[i];
+  return out;
+}
+
+void addLabelRoutes(const LinkState& ls, const std::string& area, const std::string& me,
+                    const uint32_t* dist, const uint32_t* nh, size_t Sn, int W,
+                    DecisionRouteDb& db) {
+  const std::vector<uint64_t> wide = widenDist(dist, Sn);
+  LabelRoutes labelToNode;
+  addNodeLabelRoutes(ls, ls.flat(), area, me, wide.data(), nh, Sn, W, labelToNode);
+  for (auto& [label, ne] : labelToNode) db.mplsRoutes.emplace(label, std::move(ne.second));
+}
+
+}  // namespace
+
+void LinkFailureSweep::addBaseLabelRoutes(DecisionRouteDb& db) const {
+  addLabelRoutes(ls_, area_, me_, baseDist_.data(), baseNh_.data(), baseDist_.size(), W_, db);
+}
+
+// SpfSolver.cpp:352-445 + 41-54 for the labels variant v can have moved: those
+// owned by its changed nodes. Each is resolved again over ALL its owners (the
+// smallest node name with a route wins, SpfSolver.cpp:370-375), an owner's row
+// taken from its changed record when it has one, else from the base, and
+// compared with the base's entry.
+void LinkFailureSweep::addMplsUpdate(size_t v, DecisionRouteUpdate& u) const {
+  const uint32_t r0 = nodeOffsets_[v], r1 = nodeOffsets_[v + 1];
+  if (r0 == r1) return;
+  const FlatTopology& f = ls_.flat();
+  const uint32_t rb = f.rowPtr[f.id.at(me_)];
+  const size_t Sn = baseDist_.size(), total = cNodeH_.size();
+  const auto& baseMpls = baseRouteDb().mplsRoutes;
+  const uint32_t* first = cNodeH_.data() + r0;  // node ids ascending
+  const uint32_t* last = cNodeH_.data() + r1;
+  std::set<int32_t> touched;
+  for (const uint32_t* n = first; n != last; ++n) touched.insert(nodeLabel_[*n]);
+  for (const int32_t label : touched) {
+    std::optional<RibMplsEntry> now;
+    for (const uint32_t o : labelOwners_.at(label)) {
+      const uint32_t* rec = std::lower_bound(first, last, o);
+      if (rec != last && *rec == o) {
+        const size_t i = size_t(rec - cNodeH_.data());
+        now = nodeLabelEntry(f, area_, me_, rb, f.names[o], label,
+                             cNodeDistH_[i] != 0xFFFFFFFFu, cNodeDistH_[i], &cNodeNhH_[i], total,
+                             W_);
+      } else {
+        now = nodeLabelEntry(f, area_, me_, rb, f.names[o], label, baseDist_[o] != 0xFFFFFFFFu,
+                             baseDist_[o], &baseNh_[o], Sn, W_);
+      }
+      if (now) break;
+    }
+    const auto was = baseMpls.find(label);
+    if (now) {
+      if (was == baseMpls.end() || was->second != *now) {
+        u.mplsRoutesToUpdate.emplace(label, std::move(*now));
+      }
+    } else if (was != baseMpls.end()) {
+      u.mplsRoutesToDelete.push_back(label);
+    }
+  }
+}
+
+DecisionRouteUpdate LinkFailureSweep::mplsUpdate(size_t v) const {
+  if (v >= numVariants()) throw std::out_of_range("LinkFailureSweep: variant");
+  DecisionRouteUpdate u;
+  if (!labels_) return u;
+  if (copies()) {
+    if (v >= xUpd_.size()) throw std::logic_error("LinkFailureSweep: nothing fetched yet");
+    u.mplsRoutesToUpdate = xUpd_[v].mplsRoutesToUpdate;
+    u.mplsRoutesToDelete = xUpd_[v].mplsRoutesToDelete;
+  } else if (nodeOffsets_.size() == numVariants() + 1) {
+    addMplsUpdate(v, u);
+  } else if (dist_.size() == numVariants() * baseDist_.size() && !dist_.empty()) {
+    // fetchRecords: the variant's whole label table against the base's
+    DecisionRouteDb db;
+    if (counts_[2 * v] == OGS_WHATIF_REFUSED) return u;  // wrote no rows
+    const size_t Sn = baseDist_.size();
+    addLabelRoutes(ls_, area_, me_, &dist_[v * Sn], &nh_[v * W_ * Sn], Sn, W_, db);
+    DecisionRouteDb baseLabels;
+    baseLabels.mplsRoutes = baseRouteDb().mplsRoutes;
+    u = baseLabels.calculateUpdate(db);
+  } else {
+    throw std::logic_error("LinkFailureSweep: nothing fetched yet");
+  }
+  return u;
+}
+
+std::pair<uint32_t, uint32_t> LinkFailureSweep::mplsCounts(size_t v) const {
+  const DecisionRouteUpdate u = mplsUpdate(v);
+  return {uint32_t(u.mplsRoutesToUpdate.size()), uint32_t(u.mplsRoutesToDelete.size())};
+}
+
+std::vector<int32_t> LinkFailureSweep::changedLabels(size_t v) const {
+  const DecisionRouteUpdate u = mplsUpdate(v);
+  std::vector<int32_t> out = u.mplsRoutesToDelete;
+  for (const auto& [label, _] : u.mplsRoutesToUpdate) out.push_back(label);
+  std::sort(out.begin(), out.end());
+  return out;
 }
 
 namespace {
@@ -930,7 +1155,10 @@ DecisionRouteUpdate LinkFailureSweep::routeUpdate(size_t v) const {
   }
   if (copies()) return xUpd_.at(v);
   const FlatTopology& f = ls_.flat();
-  return updateOf(f, f.rowPtr[f.id.at(me_)], me_, table_, changeRecords(), v, v4OverV6_);
+  DecisionRouteUpdate u =
+      updateOf(f, f.rowPtr[f.id.at(me_)], me_, table_, changeRecords(), v, v4OverV6_);
+  if (labels_) addMplsUpdate(v, u);
+  return u;
 }
 
 std::vector<DecisionRouteUpdate> LinkFailureSweep::routeUpdates(int threads) const {
@@ -939,7 +1167,11 @@ std::vector<DecisionRouteUpdate> LinkFailureSweep::routeUpdates(int threads) con
     throw std::out_of_range("LinkFailureSweep::routeUpdates: fetchUpdates first");
   }
   if (copies()) return xUpd_;
-  return materializeUpdates(ls_.flat(), me_, table_, changeRecords(), v4OverV6_, threads);
+  std::vector<DecisionRouteUpdate> out =
+      materializeUpdates(ls_.flat(), me_, table_, changeRecords(), v4OverV6_, threads);
+  // label routes: a few records a variant, on the caller's thread
+  for (size_t v = 0; labels_ && v < V; ++v) addMplsUpdate(v, out[v]);
+  return out;
 }
 
 DecisionRouteDb LinkFailureSweep::routeDb(size_t v) const {
@@ -957,6 +1189,14 @@ DecisionRouteDb LinkFailureSweep::routeDb(size_t v) const {
                               &mask_[v * W_ * Sp_ + p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE,
                               OGS_POLICY_NONE);
     if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
+  }
+  if (labels_) {
+    const size_t Sn = baseDist_.size();
+    if (counts_[2 * v] == OGS_WHATIF_REFUSED) {  // wrote no rows: no MPLS change
+      db.mplsRoutes = baseRouteDb().mplsRoutes;
+    } else {
+      addLabelRoutes(ls_, area_, me_, &dist_[v * Sn], &nh_[v * W_ * Sn], Sn, W_, db);
+    }
   }
   return db;
 }

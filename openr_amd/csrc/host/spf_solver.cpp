@@ -805,6 +805,38 @@ DecisionRouteDb materializeRouteDb(
   return rdb;
 }
 
+std::optional<RibMplsEntry> nodeLabelEntry(const FlatTopology& f, const std::string& area,
+                                           const std::string& me, uint32_t rb,
+                                           const std::string& node, int32_t label, bool reached,
+                                           uint64_t dist, const uint32_t* nhWords,
+                                           size_t nhStride, int W) {
+  if (node == me) {
+    NextHopThrift nh;
+    nh.address = "::";
+    nh.area = area;
+    nh.mplsAction = MplsAction{POP_AND_LOOKUP, std::nullopt, std::nullopt};
+    return RibMplsEntry{label, {nh}};
+  }
+  if (!reached) return std::nullopt;  // no route to the owner
+  RibMplsEntry entry{label, {}};
+  const int32_t m32 = static_cast<int32_t>(dist);
+  for (int w = 0; w < W; ++w) {
+    uint32_t bits = nhWords[w * nhStride];
+    while (bits) {
+      const int b = __builtin_ctz(bits);
+      bits &= bits - 1;
+      const Link& l = *f.edgeLink[rb + w * 32 + b];
+      const bool php = l.getOtherNodeName(me) == node;
+      entry.nexthops.insert(makeNh(
+          l, me, false, m32,
+          php ? MplsAction{PHP, std::nullopt, std::nullopt}
+              : MplsAction{SWAP, label, std::nullopt}));
+    }
+  }
+  if (entry.nexthops.empty()) return std::nullopt;
+  return entry;
+}
+
 void addNodeLabelRoutes(const LinkState& ls, const FlatTopology& f,
                         const std::string& area, const std::string& me,
                         const uint64_t* dist, const uint32_t* nhWords,
@@ -813,44 +845,25 @@ void addNodeLabelRoutes(const LinkState& ls, const FlatTopology& f,
   // SpfSolver.cpp:357-437, one area; dist == nullptr: the source has no
   // SPF in this area (no adjacency database), every other owner unreachable
   const auto sIt = f.id.find(me);
+  const bool spf = dist && sIt != f.id.end();
+  const uint32_t rb = spf ? f.rowPtr[sIt->second] : 0u;
   for (const auto& [node, adjDb] : ls.getAdjacencyDatabases()) {
     const int32_t label = adjDb.nodeLabel;
-    const bool valid =
-        (static_cast<uint32_t>(label) & 0xfff00000u) == 0 && label != 0;
-    if (!valid) continue;
+    if (!validNodeLabel(label)) continue;
     auto it = labelToNode.find(label);
     if (it != labelToNode.end() && it->second.first < node) continue;
+    std::optional<RibMplsEntry> entry;
     if (node == me) {
-      NextHopThrift nh;
-      nh.address = "::";
-      nh.area = area;
-      nh.mplsAction = MplsAction{POP_AND_LOOKUP, std::nullopt, std::nullopt};
-      labelToNode.erase(label);
-      labelToNode.emplace(label, std::make_pair(me, RibMplsEntry{label, {nh}}));
-      continue;
+      entry = nodeLabelEntry(f, area, me, rb, node, label, true, 0, nullptr, 0, 0);
+    } else if (spf) {
+      const uint32_t v = f.id.at(node);
+      entry = nodeLabelEntry(f, area, me, rb, node, label,
+                             reach ? bitAt(reach, v) : dist[v] != ~0ull, dist[v], nhWords + v,
+                             nhStride, W);
     }
-    if (!dist || sIt == f.id.end()) continue;
-    const uint32_t v = f.id.at(node);
-    if (reach ? !bitAt(reach, v) : dist[v] == ~0ull) continue;  // no route to the owner
-    RibMplsEntry entry{label, {}};
-    const int32_t m32 = static_cast<int32_t>(dist[v]);
-    const uint32_t rb = f.rowPtr[sIt->second];
-    for (int w = 0; w < W; ++w) {
-      uint32_t bits = nhWords[w * nhStride + v];
-      while (bits) {
-        const int b = __builtin_ctz(bits);
-        bits &= bits - 1;
-        const Link& l = *f.edgeLink[rb + w * 32 + b];
-        const bool php = l.getOtherNodeName(me) == node;
-        entry.nexthops.insert(makeNh(
-            l, me, false, m32,
-            php ? MplsAction{PHP, std::nullopt, std::nullopt}
-                : MplsAction{SWAP, label, std::nullopt}));
-      }
-    }
-    if (entry.nexthops.empty()) continue;
+    if (!entry) continue;
     labelToNode.erase(label);
-    labelToNode.emplace(label, std::make_pair(node, std::move(entry)));
+    labelToNode.emplace(label, std::make_pair(node, std::move(*entry)));
   }
 }
 

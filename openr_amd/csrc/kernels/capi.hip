@@ -609,6 +609,56 @@ int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
   return e == hipSuccess ? OGS_OK : hipFail(e, "route changes gather");
 }
 
+int ogs_spf_node_diff(const ogs_graph* graph, const ogs_unit* units, int32_t n_units,
+                      const ogs_spf_out* rows, const ogs_node_diff* diff, uint32_t flags,
+                      int32_t nh_words, void* stream) {
+  if (n_units < 0) return fail(OGS_E_INVALID, "n_units < 0");
+  if (n_units == 0) return OGS_OK;
+  if (!graph || !units || !rows || !diff) {
+    return fail(OGS_E_INVALID, "graph/units/rows/diff is NULL");
+  }
+  if (!graph->node_base) return fail(OGS_E_INVALID, "graph needs node_base");
+  if (!rows->dist || !rows->nh) return fail(OGS_E_INVALID, "rows need dist and nh");
+  if (!diff->base_dist || !diff->base_nh || !diff->changed || !diff->counts) {
+    return fail(OGS_E_INVALID, "diff needs base_dist, base_nh, changed and counts");
+  }
+  if (flags & OGS_F_WIDE_METRIC) {
+    return fail(OGS_E_UNSUPPORTED, "the node diff takes 32-bit distances");
+  }
+  if (nh_words != 1 && nh_words != 2 && nh_words != 4) {
+    return fail(OGS_E_UNSUPPORTED, "nh_words must be 1, 2 or 4");
+  }
+  if (graph->max_nodes <= 0 || uint32_t(graph->max_nodes) > OGS_MAX_NODES_PER_TOPO) {
+    return fail(OGS_E_UNSUPPORTED, "max_nodes outside (0, 2^21]");
+  }
+  hipError_t e = ogs::launch_spf_node_diff(*graph, units, n_units,
+                                           static_cast<const uint32_t*>(rows->dist), rows->nh,
+                                           nh_words, *diff, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? OGS_OK : hipFail(e, "spf node diff");
+}
+
+int ogs_spf_node_changes_gather(const uint32_t* changed, int32_t n_units, int32_t max_nodes,
+                                const ogs_spf_out* rows, int32_t nh_words,
+                                const ogs_node_changes* changes, void* stream) {
+  if (n_units < 0 || max_nodes < 0) return fail(OGS_E_INVALID, "n_units or max_nodes < 0");
+  if (n_units == 0 || max_nodes == 0) return OGS_OK;
+  if (!changed || !rows || !changes || !changes->offsets) {
+    return fail(OGS_E_INVALID, "changed/rows/changes/offsets is NULL");
+  }
+  if (!rows->dist || !rows->nh) return fail(OGS_E_INVALID, "rows need dist and nh");
+  if (nh_words != 1 && nh_words != 2 && nh_words != 4) {
+    return fail(OGS_E_UNSUPPORTED, "nh_words must be 1, 2 or 4");
+  }
+  if (changes->total == 0) return OGS_OK;
+  if (!changes->node || !changes->dist || !changes->nh) {
+    return fail(OGS_E_INVALID, "change record arrays are NULL");
+  }
+  hipError_t e = ogs::launch_spf_node_changes(
+      changed, n_units, max_nodes, nh_words, static_cast<const uint32_t*>(rows->dist), rows->nh,
+      *changes, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? OGS_OK : hipFail(e, "spf node changes gather");
+}
+
 int ogs_route_delta(const ogs_spf_out* prev, const ogs_spf_out* next, int32_t num_prefixes,
                     const uint32_t* adv_off, const uint32_t* adv_class,
                     const ogs_route_delta_policy* policy, uint32_t flags, int32_t nh_words,

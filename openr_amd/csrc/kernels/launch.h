@@ -86,6 +86,13 @@ hipError_t launch_route_delta(const ogs_spf_out& prev, const ogs_spf_out& next, 
                               const ogs_route_delta_policy* policy, bool wide, int W,
                               const ogs_route_delta_out& out, void* workspace,
                               hipStream_t stream);
+// spf_node_delta.hip
+hipError_t launch_spf_node_diff(const ogs_graph& g, const ogs_unit* units, int nUnits,
+                                const uint32_t* dist, const uint32_t* nh, int W,
+                                const ogs_node_diff& diff, hipStream_t stream);
+hipError_t launch_spf_node_changes(const uint32_t* changed, int nUnits, int Sn, int W,
+                                   const uint32_t* dist, const uint32_t* nh,
+                                   const ogs_node_changes& out, hipStream_t stream);
 // csr_patch.hip
 hipError_t launch_csr_patch(uint64_t* edges, const uint32_t* idx, const uint64_t* val,
                             int n, hipStream_t stream);

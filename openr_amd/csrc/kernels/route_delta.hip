@@ -54,24 +54,6 @@ struct DeltaSide {  // one build's records (rows of P) + optional policy columns
   const uint16_t* counter;
 };
 
-// four consecutive elements from q: one vector load on aligned rows, else
-// element loads with the bound checked (0 past the end)
-template <typename T>
-__device__ __forceinline__ void load4(const T* base, uint32_t q, uint32_t P, bool vec,
-                                      T (&v)[4]) {
-  if (vec && q + 3u < P) {
-    struct alignas(sizeof(T) * 4 > 16 ? 16 : sizeof(T) * 4) Quad {
-      T x[4];
-    };
-    const Quad t = *reinterpret_cast<const Quad*>(base + q);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = t.x[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = q + uint32_t(j) < P ? base[q + uint32_t(j)] : T(0);
-  }
-}
-
 __device__ __forceinline__ bool no_route_reason(uint32_t meta) {
   if (meta & OGS_ROUTE_VALID) return false;
   const uint32_t r = (meta >> OGS_ROUTE_REASON_SHIFT) & 0xFu;
@@ -150,12 +132,6 @@ __global__ __launch_bounds__(kDeltaBlock) void route_delta_mark_kernel(
   if (noRoute) atomicAdd(&sStats[3], noRoute);
   __syncthreads();
   if (tid < 4) stats[size_t(blockIdx.x) * 4 + tid] = sStats[tid];
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 template <int W, typename M>

@@ -33,6 +33,31 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t c, uint32_t lan
   return incl;
 }
 
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// Four consecutive elements from q of a row of P (the row diffs): one vector
+// load on aligned rows, else element loads with the bound checked (0 past the
+// end).
+template <typename T>
+__device__ __forceinline__ void load4(const T* base, uint32_t q, uint32_t P, bool vec,
+                                      T (&v)[4]) {
+  if (vec && q + 3u < P) {
+    struct alignas(sizeof(T) * 4 > 16 ? 16 : sizeof(T) * 4) Quad {
+      T x[4];
+    };
+    const Quad t = *reinterpret_cast<const Quad*>(base + q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = t.x[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = q + uint32_t(j) < P ? base[q + uint32_t(j)] : T(0);
+  }
+}
+
 template <typename D>
 struct DistInf {
   static constexpr D value = ~D(0);

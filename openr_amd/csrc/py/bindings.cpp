@@ -2291,13 +2291,15 @@ PYBIND11_MODULE(_decision, m) {
   py::class_<LinkFailureSweep>(m, "LinkFailureSweep")
       .def(py::init([toScenario](const std::string& me, const LinkState& ls,
                                  const PrefixState& ps, const std::vector<py::dict>& scenarios,
-                                 bool enableV4, bool brs) {
+                                 bool enableV4, bool brs, bool labels) {
              std::vector<LinkFailureSweep::Scenario> scs;
              for (const auto& d : scenarios) scs.push_back(toScenario(d));
-             return std::make_unique<LinkFailureSweep>(me, ls, ps, scs, enableV4, brs);
+             return std::make_unique<LinkFailureSweep>(me, ls, ps, scs, enableV4, brs, false,
+                                                       labels);
            }),
            py::arg("me"), py::arg("linkState"), py::arg("prefixState"), py::arg("scenarios"),
            py::arg("enableV4"), py::arg("enableBestRouteSelection") = false,
+           py::arg("enableNodeSegmentLabel") = false,
            py::keep_alive<1, 3>(), py::keep_alive<1, 4>())
       .def("setMode", [](LinkFailureSweep& s, int m) {
              if (m < 0 || m > 2) throw std::invalid_argument("mode must be 0, 1 or 2");
@@ -2343,6 +2345,10 @@ PYBIND11_MODULE(_decision, m) {
            }, py::arg("threads") = 0, py::call_guard<py::gil_scoped_release>())
       .def("counts", &LinkFailureSweep::counts)
       .def("changedPrefixes", &LinkFailureSweep::changedPrefixes)
+      .def("mplsCounts", &LinkFailureSweep::mplsCounts)
+      .def("changedLabels", &LinkFailureSweep::changedLabels)
+      .def("totalChangedNodes", &LinkFailureSweep::totalChangedNodes)
+      .def("flags", &LinkFailureSweep::flags)
       .def("totalChanges", &LinkFailureSweep::totalChanges)
       .def("numVariants", &LinkFailureSweep::numVariants)
       .def("nhWords", &LinkFailureSweep::nhWords)

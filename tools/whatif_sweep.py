@@ -44,7 +44,15 @@ restorations. With --g1 --restore the first three on the G1 WAN, 2,000
 scenarios each, as (p), (q), (r) in the global-state form (restoring units take
 no exit).
 
-  python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg]
+With --labels (also with --g1 and --restore) every node carries the node label
+100000 + id and each row is timed twice, interleaved: the sweep as above and
+the same sweep with enableNodeSegmentLabel. The oracle's solver then builds the
+label routes too and the sample is compared with MPLS included
+(tests/whatif_labels.py); the row adds launch + fetch with labels, the bytes of
+SPF rows the launch wrote (4 (1 + W) S_n per scenario) and the changed-node
+total.
+
+  python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg] [--labels]
   python tools/whatif_sweep.py --g1 [--nodes 20000] [--sample 64] [--sets hijkl]
   python tools/whatif_sweep.py --restore [--g1] [--sets mnos | pqr]"""
 import argparse
@@ -92,6 +100,9 @@ def main():
     ap.add_argument("--drain-every", type=int, default=2,
                     help="the baseline drains every Nth node hard and every Nth (the next one) "
                          "soft; 2 (default): every other node each")
+    ap.add_argument("--labels", action="store_true",
+                    help="node label 100000 + id on every node; each set also with "
+                         "enableNodeSegmentLabel, the sample compared with MPLS included")
     args = ap.parse_args()
     if args.sets is None:
         if args.restore:
@@ -105,6 +116,7 @@ def main():
     import openr_amd
     import whatif as W
     import whatif_metric as WM
+    import whatif_labels as WL
     import whatif_restore as WR
     from openr_amd.workloads import (C4_DUAL_PERMILLE, C4_OPTS, C4_SEED, C4_SOURCE,
                                      C4_VARIANTS)
@@ -132,6 +144,9 @@ def main():
             w.adjdbs[n]["nodeMetricIncrementVal"] = 1000
             for a in w.adjdbs[n]["adjacencies"]:
                 a["metric"] += 1000
+    if args.labels:
+        for n, d in w.adjdbs.items():
+            d["nodeLabel"] = 100000 + int(n)
     rng = random.Random(0xC4F)
 
     def both(n, ifn, metric):  # the link behind (n, ifn): both directions sent with `metric`
@@ -181,7 +196,7 @@ def main():
           f"{w.directed_edges()} directed edges, "
           f"source {me}, mode kChangedOnly unless a row says kFull")
     als, ls, ps = w.load(M, me)
-    oracle = W.Oracle(O, w, me)
+    oracle = (WL.LabelOracle if args.labels else W.Oracle)(O, w, me)
     base, weight, far = {}, {}, {}  # the exit-only rule's inputs: the G1 rows alone
     if args.g1:
         base = {n: r[0] for n, r in oracle.ls.getSpfResult(me).items()}  # reached nodes' distances
@@ -213,11 +228,13 @@ def main():
     for label, scs, ab, modes in sets:
         sweeps, names = [], []  # one sweep and its row label per (mode, list form)
         for force, mode in [(f, m) for m in modes for f in ((False, True) if ab else (False,))]:
-            sw = M.LinkFailureSweep(me, ls, ps, scs, True, False)
-            sw.setMode(mode)
-            sw.setListForm(force)
-            sweeps.append(sw)
-            names.append(label if mode == 2 else label + " (kFull)")
+            for on in ((False, True) if args.labels else (False,)):
+                sw = M.LinkFailureSweep(me, ls, ps, scs, True, False, enableNodeSegmentLabel=on)
+                sw.setMode(mode)
+                sw.setListForm(force)
+                sweeps.append(sw)
+                names.append((label if mode == 2 else label + " (kFull)") +
+                             (" +labels" if on else ""))
         # interleaved: one timed series per sweep, alternating
         ms = [[] for _ in sweeps]
         for i in range(7):
@@ -236,7 +253,17 @@ def main():
         for _, canon in answers:
             digest.update(canon)
         for k, sw in enumerate(sweeps):
-            W.check_sweep(sw, answers, label, idx)  # raises on any difference
+            # raises on any difference; beside a labelled oracle the label-free
+            # sweep is compared on its unicast counts alone (its RouteDbs carry
+            # no MPLS routes, the oracle's do)
+            if names[k].endswith("+labels"):
+                WL.check_labels(sw, answers, label, idx)
+            elif args.labels:
+                for i, (want, _) in zip(idx, answers):
+                    assert tuple(sw.counts(i)) == (len(want["unicastRoutesToUpdate"]),
+                                                   len(want["unicastRoutesToDelete"])), (label, i)
+            else:
+                W.check_sweep(sw, answers, label, idx)
             n, mat_ms = sw.materializeAll(0)
             row = dict(set=names[k], scenarios=len(scs), form=FORMS[sw.form()],
                        sweep_ms=median(ms[k][2:]), materialize_ms=mat_ms, changed_routes=n,
@@ -244,13 +271,18 @@ def main():
                        sample=len(idx), sample_digest=digest.hexdigest()[:16])
             if args.g1:
                 row["exit_only_share"] = sum(exit_only(sc) for sc in scs) / len(scs)
+            if names[k].endswith("+labels"):
+                row["row_bytes"] = 4 * (1 + sw.nhWords()) * len(w.adjdbs) * len(scs)
+                row["changed_nodes"] = sw.totalChangedNodes()
             out.append(row)
             print(f"  {row['set']:26s} {len(scs):6d} scenarios  {row['form']:15s} "
                   f"launch+fetch {row['sweep_ms']:8.3f} ms  materialise {mat_ms:8.3f} ms  "
                   f"changed routes {n:9d}  | oracle loop {cpu_ms:7.3f} ms/scenario x "
                   f"{len(scs)} = {cpu_ms * len(scs) / 1e3:8.2f} s (extrapolated from "
                   f"{len(idx)}); sample equal, sha1 {row['sample_digest']}" +
-                  (f"; exit-only units {100 * row['exit_only_share']:.1f} %" if args.g1 else ""))
+                  (f"; exit-only units {100 * row['exit_only_share']:.1f} %" if args.g1 else "") +
+                  (f"; SPF rows {row['row_bytes'] / 1e6:.1f} MB, changed nodes "
+                   f"{row['changed_nodes']}" if "row_bytes" in row else ""))
     print(json.dumps(dict(workload="g1_whatif_sweep" if args.g1 else "c4_whatif_sweep", nodes=len(w.adjdbs), rows=out)))
 
 
