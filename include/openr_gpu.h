@@ -768,7 +768,10 @@ typedef struct ogs_route_changes {
 
 /* Gathers the changed records (diff->changed bitmap of the same call's
  * units, out->meta/metric/mask records of ogs_spf_routes_variants) into
- * `changes`. nh_words 1, 2 or 4 as for the variants call. */
+ * `changes`. nh_words 1, 2 or 4 as for the variants call. A unit's bitmap
+ * row holds ceil(max_prefixes / 32) words; bits at or past max_prefixes are
+ * ignored. A unit never writes at or past offsets[u + 1]: of a unit with more
+ * set bits than its slice holds, the first ones are gathered. */
 int ogs_route_changes_gather(const uint32_t* changed, int32_t n_units,
                              int32_t max_prefixes, const ogs_spf_out* records,
                              int32_t nh_words, const ogs_route_changes* changes,
@@ -945,8 +948,14 @@ typedef struct ogs_rib_policy {
  * counterID the route carries (the last matching one tried), OGS_POLICY_NONE
  * = none. Statement ids are u16: a policy of up to 65,535 statements runs in
  * chunks of 32 (statement_base).
- * The prefix table is one topology's (pfx_base[0..1]); single-area callers
- * pass num_areas = 1. */
+ * The prefix table is one topology's (pfx_base[0..1]: pfx_match and adv_off
+ * are read at the global prefix pfx_base[0] + p, adv_tag_match at the global
+ * entry adv_off[pfx_base[0] + p] + best); single-area callers pass
+ * num_areas = 1. meta is only read; a route without
+ * OGS_ROUTE_VALID keeps its masks and gets OGS_POLICY_NONE twice (a
+ * continuation chunk leaves its counter as it came). Columns p >= the table's
+ * prefix count (pfx_base[1] - pfx_base[0]) of mask, applied and counter are
+ * not written. applied and counter may be NULL when statement_base is 0. */
 int ogs_rib_policy_apply(const ogs_prefix_table* prefixes,
                          const ogs_rib_policy* policy, int32_t num_areas,
                          int32_t n_units, int32_t nh_words,
@@ -966,7 +975,14 @@ int ogs_rib_policy_apply(const ogs_prefix_table* prefixes,
  * SPF launch's width, e.g. after OGS_F_EXACT_ORDER). Replaces createRouteForPrefix across areas
  * (SpfSolver.cpp:160-311: per-area reachability, selectBestRoutes 455-486,
  * areas with best routes, getNextHopsWithMetric per area 648-688, minimum
- * metric union over areas, addBestPaths 595-639). */
+ * metric union over areas, addBestPaths 595-639).
+ * A record without OGS_ROUTE_VALID holds the state at the reference's
+ * return: OGS_REASON_V4_DISABLED meta = the reason alone; _UNREACHABLE adds
+ * OGS_ROUTE_LOCAL; both with an all-ones metric, sel 0 and zero masks.
+ * _SELF carries LOCAL, SELECTED, the best index, DRAINED and sel, an all-ones
+ * metric and zero masks. _NO_NEXTHOP and _MIN_NEXTHOP carry those bits, sel,
+ * and the metric and masks addBestPaths was handed. Columns p >= the table's
+ * prefix count (pfx_base[1] - pfx_base[0]) are not written. */
 int ogs_routes_multiarea(const ogs_graph* graph,
                          const ogs_prefix_table* prefixes,
                          const ogs_area_table* areas,

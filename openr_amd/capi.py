@@ -129,6 +129,29 @@ class NodeChanges(ctypes.Structure):
                 ("nh", ctypes.c_void_p)]
 
 
+class RibPolicy(ctypes.Structure):
+    """ogs_rib_policy: one chunk of <= 32 statements compiled against a
+    prefix table (device pointers)."""
+    _fields_ = [("num_statements", ctypes.c_int32), ("active", ctypes.c_uint32),
+                ("pfx_match", ctypes.c_void_p), ("adv_tag_match", ctypes.c_void_p),
+                ("slot_nonzero", ctypes.c_void_p), ("statement_base", ctypes.c_int32)]
+
+
+class AreaTable(ctypes.Structure):
+    """ogs_area_table: the name-id tables of a multi-area domain and the
+    optional settled bitsets of its SPF rows."""
+    _fields_ = [("num_areas", ctypes.c_int32), ("num_names", ctypes.c_int32),
+                ("name_local", ctypes.c_void_p), ("adv_area", ctypes.c_void_p),
+                ("adv_name", ctypes.c_void_p), ("reached", ctypes.c_void_p)]
+
+
+class RouteChanges(ctypes.Structure):
+    """ogs_route_changes: offsets, total and the compact record arrays."""
+    _fields_ = [("offsets", ctypes.c_void_p), ("total", ctypes.c_size_t),
+                ("prefix", ctypes.c_void_p), ("meta", ctypes.c_void_p),
+                ("metric", ctypes.c_void_p), ("mask", ctypes.c_void_p)]
+
+
 def route_delta_workspace_bytes(num_prefixes):
     """OGS_ROUTE_DELTA_WORKSPACE_BYTES of include/openr_gpu.h."""
     return (num_prefixes + OGS_ROUTE_DELTA_TILE - 1) // OGS_ROUTE_DELTA_TILE * 528
@@ -209,6 +232,10 @@ def load(path=None):
     lib.ogs_spf_node_changes_gather.argtypes = [
         P, I32, I32, ctypes.POINTER(SpfOut), I32, ctypes.POINTER(NodeChanges), P]
     lib.ogs_spf_node_changes_gather.restype = ctypes.c_int
+    # changed-route gather of the variant / scenario / what-if sweeps
+    lib.ogs_route_changes_gather.argtypes = [
+        P, I32, I32, ctypes.POINTER(SpfOut), I32, ctypes.POINTER(RouteChanges), P]
+    lib.ogs_route_changes_gather.restype = ctypes.c_int
     return lib
 
 

@@ -196,28 +196,12 @@ class PathOut(ctypes.Structure):
                 ("max_edges", ctypes.c_uint32)]
 
 
-class AreaTable(ctypes.Structure):
-    _fields_ = [("num_areas", ctypes.c_int32), ("num_names", ctypes.c_int32),
-                ("name_local", ctypes.c_void_p), ("adv_area", ctypes.c_void_p),
-                ("adv_name", ctypes.c_void_p), ("reached", ctypes.c_void_p)]
-
-
 class UnitMods(ctypes.Structure):
     _fields_ = [("dead_edges", ctypes.c_void_p), ("dead_per_unit", ctypes.c_int32)]
 
 
-class RouteDiff(ctypes.Structure):
-    _fields_ = [("base_meta", ctypes.c_void_p), ("base_metric", ctypes.c_void_p),
-                ("base_mask", ctypes.c_void_p), ("changed", ctypes.c_void_p),
-                ("counts", ctypes.c_void_p), ("base_dist", ctypes.c_void_p),
-                ("base_nh", ctypes.c_void_p), ("adv_class", ctypes.c_void_p),
-                ("base_desc", ctypes.c_void_p), ("base_desc_valid", ctypes.c_int32)]
-
-
-class RibPolicy(ctypes.Structure):
-    _fields_ = [("num_statements", ctypes.c_int32), ("active", ctypes.c_uint32),
-                ("pfx_match", ctypes.c_void_p), ("adv_tag_match", ctypes.c_void_p),
-                ("slot_nonzero", ctypes.c_void_p), ("statement_base", ctypes.c_int32)]
+# ogs_area_table, ogs_route_diff and ogs_rib_policy: openr_amd.capi's
+# AreaTable, RouteDiff and RibPolicy
 
 
 def _struct(cls, base, **over):
@@ -246,18 +230,18 @@ def bad_argument_cases(lib, capi):
                                                   max_paths=4, max_edges=40), **kw))
 
     def areas(**kw):
-        return ctypes.byref(_struct(AreaTable, dict(num_areas=1, num_names=10, name_local=X,
+        return ctypes.byref(_struct(capi.AreaTable, dict(num_areas=1, num_names=10, name_local=X,
                                                     adv_area=X, adv_name=X), **kw))
 
     def mods(**kw):
         return ctypes.byref(_struct(UnitMods, dict(dead_edges=X, dead_per_unit=2), **kw))
 
     def diff(**kw):
-        return ctypes.byref(_struct(RouteDiff, dict(base_meta=X, base_metric=X, base_mask=X,
+        return ctypes.byref(_struct(capi.RouteDiff, dict(base_meta=X, base_metric=X, base_mask=X,
                                                     changed=X, counts=X), **kw))
 
     def policy(**kw):
-        return ctypes.byref(_struct(RibPolicy, dict(num_statements=2, active=3, pfx_match=X,
+        return ctypes.byref(_struct(capi.RibPolicy, dict(num_statements=2, active=3, pfx_match=X,
                                                     adv_tag_match=X, slot_nonzero=X), **kw))
 
     def groups(*specs):
