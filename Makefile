@@ -74,7 +74,7 @@ ASAN_REF := build/asan/_refcpu$(EXT)
 ASAN_LOG ?= profiles/r06_asan.log
 ASAN_STUBS := tests/asan/ogs_stub.cpp tests/asan/ogs_stub_delta.cpp tests/asan/ogs_stub_scenarios.cpp \
   tests/asan/ogs_stub_whatif.cpp tests/asan/ogs_stub_whatif_global.cpp \
-  tests/asan/ogs_stub_node_diff.cpp
+  tests/asan/ogs_stub_node_diff.cpp tests/asan/ogs_stub_whatif_pairs.cpp
 $(ASAN_BIN): $(HOST) $(HOST_H) tests/asan/host_asan.cpp $(ASAN_STUBS)
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
@@ -107,6 +107,16 @@ $(ASAN_RESTORE): $(HOST) $(HOST_H) tests/asan/restore_asan.cpp $(ASAN_STUBS)
 	  -o $@ -lpthread
 asan-restore: $(ASAN_RESTORE)
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_RESTORE)
+# the network-wide sweep's plan (pairs, skipped pairs, chunks, fallback split),
+# same stubs; `make asan-network` builds and runs this program alone
+ASAN_NETWORK := build/asan/network_asan
+$(ASAN_NETWORK): $(HOST) $(HOST_H) tests/asan/network_asan.cpp $(ASAN_STUBS)
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SAN) -Wall -Wno-unused-function -Iinclude -Iopenr_amd/csrc/host \
+	  $(HOST) tests/asan/network_asan.cpp $(ASAN_STUBS) \
+	  -o $@ -lpthread
+asan-network: $(ASAN_NETWORK)
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 ./$(ASAN_NETWORK)
 $(ASAN_REF): oracle/refcpu/refcpu.cpp oracle/refcpu/refcpu.h oracle/refcpu/bindings.cpp openr_amd/csrc/gen/topogen.h
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SAN) -fPIC -shared -I$(PY_INC) -I$(PYBIND_INC) \
@@ -124,4 +134,4 @@ clean:
 	rm -f $(LIB) $(MOD) $(STAMPS) $(CCONS) $(KOBJ) $(SOBJ)
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean stamps asan asan-whatif asan-restore
+.PHONY: all oracle clean stamps asan asan-whatif asan-restore asan-network

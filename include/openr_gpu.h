@@ -58,7 +58,9 @@ extern "C" {
  * scenario sweep on also export ogs_spf_routes_scenarios /
  * ogs_ctx_spf_routes_scenarios, and from the metric / soft-drain sweep on
  * ogs_spf_routes_whatif / ogs_ctx_spf_routes_whatif, and from the node-label
- * sweep on ogs_spf_node_diff / ogs_spf_node_changes_gather (the "ABI 9"
+ * sweep on ogs_spf_node_diff / ogs_spf_node_changes_gather, and from the
+ * network-wide sweep on ogs_spf_routes_whatif_pairs /
+ * ogs_ctx_spf_routes_whatif_pairs (the "ABI 9"
  * additions: the number stays 8 because they change no existing entry); a
  * consumer that may meet an older ABI-8 library detects them by symbol
  * (dlsym). */
@@ -740,6 +742,59 @@ int ogs_spf_routes_whatif_global(const ogs_graph* graph,
                                  ogs_route_diff* diff, uint32_t flags,
                                  int32_t nh_words, ogs_spf_out* out, void* stream);
 
+/* ogs_spf_routes_whatif over (source, scenario) PAIRS: which nodes' RouteDbs
+ * change under each scenario. In Open/R every node runs its own Decision, so
+ * the reference's answer is one RouteDb per node (Decision.cpp:341-360:
+ * buildRouteDb(node)) and one DecisionRouteDb::calculateUpdate
+ * (SpfSolver.cpp:21-56) per node per scenario; the scenario kinds stand for
+ * what ogs_scenario_mods and ogs_whatif_mods cite (LinkState.cpp:491-634, :643,
+ * :441, :741-752, LinkMonitor.cpp:1003-1006, :971-1001, SpfSolver.cpp:511-551
+ * and the OGS_F_RESTORE kinds' lines). Unit u (units[u].src = the source)
+ *   - writes row u of every output: diff->changed, diff->counts, out->*;
+ *   - reads its BASE at row b = pairs->base[u] of diff's base arrays:
+ *     base_dist / base_nh at b * S_n, base_meta / base_metric / base_mask at
+ *     b * S_p -- exactly what ONE ogs_spf_routes launch over the source units
+ *     at nh_words 1 writes, so no repacking is needed. By the caller's
+ *     contract units[u].src is the source of base row b;
+ *   - reads its LISTS at row k = pairs->scenario[u] of mods' offset arrays:
+ *     dead_off[k] .. dead_off[k + 1], likewise node_off and metric_off (the
+ *     offset arrays hold n_scenarios + 1 entries; they are not per unit).
+ * A unit with b >= n_bases or k >= n_scenarios is REFUSED before it indexes
+ * anything: counts {OGS_WHATIF_REFUSED, OGS_WHATIF_REFUSED}, a zero `changed`
+ * row, no record -- exactly like a unit with a bad metric value. Every mods
+ * rule and flag stays as ogs_spf_routes_whatif documents it (skipped ids, dead
+ * wins over overridden, lists ignored under OGS_F_HOP_METRIC, refused units,
+ * the OGS_F_RESTORE encodings, OGS_F_CHANGED_ONLY, `changed` zeroed by the
+ * call, the ogs_route_changes_gather contract on the outputs), and every
+ * argument rule the two entries share returns the same status, in the same
+ * order. Differences:
+ *   - the entry runs ONLY as the repair: it requires OGS_F_INCREMENTAL,
+ *     nh_words == 1, diff->base_dist and diff->base_nh, max_nodes <= 65535 and
+ *     the what-if repair's LDS budget (see ogs_spf_routes_whatif); otherwise
+ *     OGS_E_UNSUPPORTED with nothing launched. There is no full-frontier form;
+ *   - diff->base_desc is ignored and base_desc_valid is left as it came
+ *     (descendant rows are per source; the set to repair grows by list rounds);
+ *   - node bits are taken, since the repair takes them;
+ *   - pairs, pairs->base or pairs->scenario NULL, n_bases <= 0 or
+ *     n_scenarios < 0: OGS_E_INVALID. n_units == 0: OGS_OK.
+ * A caller bounds the dense outputs by calling over chunks of units: units,
+ * pairs->base, pairs->scenario, out and the diff's changed / counts rows
+ * advance per chunk; mods and the base arrays stay. */
+typedef struct ogs_whatif_pairs {
+  const uint32_t* base;      /* [n_units] device: the unit's row in diff's base arrays */
+  const uint32_t* scenario;  /* [n_units] device: the unit's row in mods' offset arrays */
+  int32_t n_bases;           /* rows of base_dist/base_nh ([n_bases*S_n]) and of
+                                base_meta/base_metric/base_mask ([n_bases*S_p]) */
+  int32_t n_scenarios;       /* mods' offset arrays hold n_scenarios + 1 entries */
+} ogs_whatif_pairs;
+int ogs_spf_routes_whatif_pairs(const ogs_graph* graph,
+                                const ogs_prefix_table* prefixes,
+                                const ogs_unit* units /* device */, int32_t n_units,
+                                const ogs_whatif_pairs* pairs,
+                                const ogs_whatif_mods* mods,
+                                ogs_route_diff* diff, uint32_t flags,
+                                int32_t nh_words, ogs_spf_out* out, void* stream);
+
 /* Host only, no device needed: 1 when the LDS forms behind
  * ogs_spf_routes_variants / _scenarios / _whatif cannot hold an area of
  * graph->max_nodes nodes at this width (they return OGS_E_UNSUPPORTED) and
@@ -1037,6 +1092,12 @@ int ogs_ctx_spf_routes_whatif(ogs_ctx* ctx, const ogs_graph* graph,
                               int32_t n_units, const ogs_whatif_mods* mods,
                               ogs_route_diff* diff, uint32_t flags, int32_t nh_words,
                               ogs_spf_out* out, void* stream);
+int ogs_ctx_spf_routes_whatif_pairs(ogs_ctx* ctx, const ogs_graph* graph,
+                                    const ogs_prefix_table* prefixes, const ogs_unit* units,
+                                    int32_t n_units, const ogs_whatif_pairs* pairs,
+                                    const ogs_whatif_mods* mods, ogs_route_diff* diff,
+                                    uint32_t flags, int32_t nh_words, ogs_spf_out* out,
+                                    void* stream);
 int ogs_ctx_ksp_paths(ogs_ctx* ctx, const ogs_graph* graph, const ogs_path_unit* units,
                       int32_t n_units, const uint32_t* masks, uint32_t mask_words,
                       uint32_t flags, ogs_path_out* out, void* stream);

@@ -38,6 +38,7 @@ EXPORTS = [
     "ogs_spf_routes_whatif", "ogs_ctx_spf_routes_whatif",
     "ogs_spf_routes_whatif_global", "ogs_whatif_needs_global",
     "ogs_spf_node_diff", "ogs_spf_node_changes_gather",
+    "ogs_spf_routes_whatif_pairs", "ogs_ctx_spf_routes_whatif_pairs",
 ]
 
 OGS_WHATIF_REFUSED = 0xFFFFFFFF
@@ -55,6 +56,13 @@ class WhatifMods(ctypes.Structure):
                 ("node_bits", ctypes.c_void_p),
                 ("metric_off", ctypes.c_void_p), ("metric_edges", ctypes.c_void_p),
                 ("metric_vals", ctypes.c_void_p), ("max_metric_per_unit", ctypes.c_uint32)]
+
+
+class WhatifPairs(ctypes.Structure):
+    """ogs_whatif_pairs: per unit, its row in the diff's base arrays and its
+    row in the mods' offset arrays (device pointers)."""
+    _fields_ = [("base", ctypes.c_void_p), ("scenario", ctypes.c_void_p),
+                ("n_bases", ctypes.c_int32), ("n_scenarios", ctypes.c_int32)]
 
 
 class Graph(ctypes.Structure):
@@ -209,6 +217,7 @@ def load(path=None):
         "ogs_spf_routes_variants": [P, P, P, I32, P, P, U32, I32, P, P],
         "ogs_spf_routes_scenarios": [P, P, P, I32, P, P, U32, I32, P, P],
         "ogs_spf_routes_whatif": [P, P, P, I32, P, P, U32, I32, P, P],
+        "ogs_spf_routes_whatif_pairs": [P, P, P, I32, P, P, P, U32, I32, P, P],
         "ogs_ksp_paths": [P, P, I32, P, U32, U32, P, P],
         "ogs_ksp2_paths": [P, P, I32, P, I32, U32, P, P, P],
         "ogs_routes_multiarea": [P, P, P, P, I32, P, P, P, U32, I32, P, P],

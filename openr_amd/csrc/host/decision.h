@@ -1184,6 +1184,10 @@ struct ChangeRecords {
 // One DecisionRouteUpdate per variant (calculateUpdate, SpfSolver.cpp:21-56:
 // records without VALID are deletions, the rest materialised routes), built
 // on `threads` host threads (0: up to 16 / the hardware's).
+// variant v's alone
+DecisionRouteUpdate materializeUpdate(const FlatTopology& f, const std::string& me,
+                                      const PrefixHostTable& pt, const ChangeRecords& c,
+                                      size_t v, bool v4OverV6Nexthop);
 std::vector<DecisionRouteUpdate> materializeUpdates(const FlatTopology& f, const std::string& me,
                                                     const PrefixHostTable& pt,
                                                     const ChangeRecords& c, bool v4OverV6Nexthop,
@@ -1322,6 +1326,35 @@ class LinkFailureSweep {
   // in nodesSoftDrained and nodesSoftUndrained; the same link, by either end,
   // in linksDown and linksUndrained. Host only.
   static Expanded expandScenario(const LinkState& ls, const std::string& me, const Scenario& sc);
+  // Every scenario's expansion as the CSR slices the device entries read
+  // (ogs_scenario_mods / ogs_whatif_mods); the lists do not depend on the
+  // source. Scenario v: dead directed edges deadList[deadOff[v] .. deadOff[v + 1])
+  // and drained nodes drainList[drainOff[v] ..); metric overrides metricEdge /
+  // metricVal[metricOff[v] ..) and flag bits flagNode / flagBits[flagOff[v] ..)
+  // (the hard drains of drainList among them). whatif: some scenario has a
+  // metric, a soft-drain bit or a restoration. restores: some scenario revives
+  // a link or clears a node bit; then metricUp[i] marks the revived entries of
+  // metricEdge (uploaded with OGS_WHATIF_EDGE_UP) and flagBits carry the
+  // cleared bits in the high nibble (OGS_NODE_CLEAR_SHIFT); launches set
+  // OGS_F_RESTORE. Host only.
+  struct Lists {
+    std::vector<uint32_t> deadOff{0}, deadList, drainOff{0}, drainList;
+    uint32_t maxDead{0};  // longest dead list
+    std::vector<uint32_t> metricOff{0}, metricEdge, flagOff{0}, flagNode;
+    std::vector<uint64_t> metricVal;
+    std::vector<uint8_t> flagBits, metricUp;
+    bool restores{false}, whatif{false};
+    uint32_t maxMetricList{0};
+    void append(const Expanded& x);
+  };
+  // What the area and the lists' weights alone decide about the form (host
+  // only): exact -> kTopologyCopies (exactOrder: in the extraction order),
+  // needsGlobal -> kGlobalState; W = the source's next-hop words.
+  struct AreaDomain {
+    bool exact{false}, exactOrder{false}, needsGlobal{false};
+  };
+  static AreaDomain areaDomain(const FlatTopology& f, const HostBatch& hb, int W,
+                               const std::vector<uint64_t>& metricVals);
   LinkFailureSweep(const std::string& myNodeName, const LinkState& ls,
                    const PrefixState& ps, const std::vector<Scenario>& scenarios,
                    bool enableV4, bool enableBestRouteSelection = false,
@@ -1377,7 +1410,7 @@ class LinkFailureSweep {
   // them (parity tests)
   void fetchRecords(void* stream = nullptr);
 
-  size_t numVariants() const { return deadOff_.size() - 1; }
+  size_t numVariants() const { return lists_.deadOff.size() - 1; }
   const DecisionRouteDb& baseRouteDb() const;             // after a launch
   DecisionRouteUpdate routeUpdate(size_t v) const;        // after fetchUpdates
   // every variant's update, materialised on `threads` host threads (0: up to
@@ -1442,24 +1475,7 @@ class LinkFailureSweep {
   bool descValid_{false};  // bDesc_ holds the base's descendant rows
   DeviceBuffer bDesc_;
   Mode mode_{kRepair};
-  // scenario v: dead directed edges deadList_[deadOff_[v] .. deadOff_[v + 1])
-  // and drained nodes drainList_[drainOff_[v] .. drainOff_[v + 1])
-  std::vector<uint32_t> deadOff_{0}, deadList_, drainOff_{0}, drainList_;
-  uint32_t maxDead_{0};  // longest dead list
-  // metric overrides metricEdge_ / metricVal_[metricOff_[v] .. metricOff_[v + 1])
-  // and flag bits flagNode_ / flagBits_[flagOff_[v] .. flagOff_[v + 1]) (the
-  // hard drains of drainList_ among them); whatif_: some scenario has either
-  std::vector<uint32_t> metricOff_{0}, metricEdge_, flagOff_{0}, flagNode_;
-  std::vector<uint64_t> metricVal_;
-  std::vector<uint8_t> flagBits_;
-  // restores_: some scenario revives a link or clears a node bit. Then
-  // metricUp_[i] marks the revived entries of metricEdge_ (uploaded with
-  // OGS_WHATIF_EDGE_UP) and flagBits_ carry the cleared bits in the high
-  // nibble (OGS_NODE_CLEAR_SHIFT); launches set OGS_F_RESTORE
-  std::vector<uint8_t> metricUp_;
-  bool restores_{false};
-  uint32_t maxMetricList_{0};
-  bool whatif_{false};
+  Lists lists_;
   DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_, dFlagOff_, dFlagNode_, dFlagBits_;
   bool forceBitset_{false};
   bool forceGlobal_{false}, needsGlobal_{false};
@@ -1493,6 +1509,125 @@ class LinkFailureSweep {
   std::vector<uint64_t> xMetric_;
   std::vector<DecisionRouteDb> xDb_;
   std::vector<DecisionRouteUpdate> xUpd_;
+};
+
+// ----------------------------------------------------- NetworkWhatifSweep --
+// Which nodes' RouteDbs change under each scenario, and how: in Open/R every
+// node runs its own Decision (Decision.cpp:341-360 serves one RouteDb per
+// node), so the reference's answer is buildRouteDb(node) + calculateUpdate
+// (SpfSolver.cpp:21-56) per node per scenario. Here every (source, scenario)
+// pair of one area is a unit of ogs_spf_routes_whatif_pairs: one base launch
+// (ogs_spf_routes over the batched sources), the scenario lists uploaded
+// once, then pair launches over chunks of units.
+//
+// The host-only plan: who is batched, the units, the chunks.
+struct NetworkWhatifPlan {
+  // source indices, ascending. Batched: ogs_nh_words_for_degree(degree) == 1
+  // on an area in the pairs entry's domain (LinkFailureSweep::areaDomain: not
+  // exact, no global-state form). Every other source runs through its own
+  // LinkFailureSweep
+  std::vector<uint32_t> batched, fallback;
+  // the batch's units {source index, scenario}, source-major, scenario
+  // ascending (consecutive workgroups share base rows)
+  std::vector<std::pair<uint32_t, uint32_t>> pairs;
+  // {source index, scenario} with the source in the scenario's nodesDown, of
+  // every source: that node runs no Decision, the pair is never launched
+  std::vector<std::pair<uint32_t, uint32_t>> sourceDown;
+  // device bytes of one unit's outputs with records (meta, metric, mask rows,
+  // the bitmap row, the counts) and impact-only (bitmap row, counts), and the
+  // chunks' unit boundaries [0, ..., pairs.size()] for either
+  size_t unitBytes{0}, impactUnitBytes{0};
+  std::vector<size_t> chunks, impactChunks;
+};
+// std::invalid_argument as LinkFailureSweep::expandScenario (but for a source
+// in nodesDown) and for a source that is not in the area. No device.
+NetworkWhatifPlan network_whatif_plan(const LinkState& ls, const PrefixState& ps,
+                                      const std::vector<std::string>& sources,
+                                      const std::vector<LinkFailureSweep::Scenario>& scenarios,
+                                      size_t chunkBytes = size_t(1) << 30);
+
+// `ls` and `ps` must outlive the sweep unchanged. Out of the batch (fallback
+// per source, or thrown as LinkFailureSweep throws): multi-area domains, node
+// segment labels, sources of more than 32 links, the exact domain, areas of
+// 16,385+ nodes.
+class NetworkWhatifSweep {
+ public:
+  NetworkWhatifSweep(const LinkState& ls, const PrefixState& ps,
+                     const std::vector<std::string>& sources,
+                     const std::vector<LinkFailureSweep::Scenario>& scenarios, bool enableV4,
+                     bool enableBestRouteSelection = false, bool v4OverV6Nexthop = false);
+  // Base launch when needed, then every chunk: pair launch and, with records,
+  // counts D2H -> host scan -> ogs_route_changes_gather -> the chunk's compact
+  // records D2H (the dense arrays are reused by the next chunk, so a launch
+  // with records returns with the batch's records on the host). records =
+  // false: bitmap and counts only (impact). Fallback sources launch their own
+  // sweeps. If the pairs entry reports the call unsupported (its LDS budget),
+  // every batched source becomes a fallback source.
+  void launch(void* stream = nullptr, bool records = true);
+  void fetchImpact(void* stream = nullptr);   // counts of every pair
+  void fetchUpdates(void* stream = nullptr);  // + the changed records (needs records)
+  size_t numSources() const { return sources_.size(); }
+  size_t numScenarios() const { return K_; }
+  size_t batchedSources() const { return plan_.batched.size(); }
+  size_t numChunks(bool records = true) const {
+    const auto& c = records ? plan_.chunks : plan_.impactChunks;
+    return c.empty() ? 0 : c.size() - 1;
+  }
+  const NetworkWhatifPlan& plan() const { return plan_; }
+  enum PairState { kComputed, kSourceDown };
+  PairState state(size_t s, size_t k) const;
+  // {update, delete}; {0, 0} for a kSourceDown pair
+  std::pair<uint32_t, uint32_t> counts(size_t s, size_t k) const;
+  // source indices whose counts(s, k) != {0, 0}, ascending
+  std::vector<uint32_t> affectedSources(size_t k) const;
+  std::vector<std::string> changedPrefixes(size_t s, size_t k) const;  // after fetchUpdates
+  // std::invalid_argument for a kSourceDown pair
+  DecisionRouteUpdate routeUpdate(size_t s, size_t k) const;
+  const DecisionRouteDb& baseRouteDb(size_t s) const;  // after a fetch
+  // device bytes of one chunk's outputs; default 1 GiB (the global form's
+  // default bound); drops fetched results
+  void setChunkBytes(size_t bytes);
+
+ private:
+  struct Fallback {
+    std::unique_ptr<LinkFailureSweep> sweep;
+    std::vector<int32_t> local;  // scenario -> the sweep's variant, -1: kSourceDown
+  };
+  void check(size_t s, size_t k) const;
+  void addFallback(size_t s);
+  void replan();
+  void runBase(void* stream);
+  bool launchChunks(void* stream, bool records);  // false: the entry refused the call
+  ChangeRecords changeRecords() const;
+  const LinkState& ls_;
+  const PrefixState& ps_;
+  std::vector<std::string> sources_;
+  std::vector<LinkFailureSweep::Scenario> scenarios_;
+  bool enableV4_, brs_, v4OverV6_;
+  size_t K_{0}, Sn_{1}, Sp_{1}, words_{1};
+  size_t chunkBytes_{size_t(1) << 30};
+  NetworkWhatifPlan plan_;
+  LinkFailureSweep::Lists lists_;
+  PrefixHostTable table_;
+  HostBatch hb_;
+  HostBatchImage img_;
+  std::vector<uint8_t> down_;     // [S * K] the pair is kSourceDown
+  std::vector<int32_t> row_;      // source -> base row, -1: fallback
+  std::vector<uint32_t> unit_;    // [rows * K] unit of (row, scenario); kNoUnit
+  static constexpr uint32_t kNoUnit = 0xFFFFFFFFu;
+  std::map<size_t, Fallback> fb_;
+  bool uploaded_{false}, baseRun_{false}, launched_{false}, records_{false};
+  bool impactFetched_{false}, updatesFetched_{false};
+  void upload();
+  DeviceBuffer dUnits_, dBase_, dScen_, dBaseUnits_, dAdvClass_;
+  DeviceBuffer dDeadOff_, dDeadList_, dFlagOff_, dFlagNode_, dFlagBits_;
+  DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_;
+  DeviceBuffer bDist_, bNh_, bMeta_, bMetric_, bMask_, bSel_;
+  DeviceBuffer dMeta_, dMetric_, dMask_, dChanged_, dCounts_;
+  DeviceBuffer dOffsets_, cPrefix_, cMeta_, cMetric_, cMask_;
+  std::vector<uint32_t> counts_, offsets_;
+  std::vector<uint32_t> cPrefixH_, cMetaH_, cMetricH_, cMaskH_;
+  mutable std::map<size_t, DecisionRouteDb> base_;
 };
 
 // ----------------------------------------------------------- RouteDbBatch --

@@ -282,10 +282,72 @@ LinkFailureSweep::Expanded LinkFailureSweep::expandScenario(const LinkState& ls,
   return x;
 }
 
+// One scenario's lists appended as CSR slices: dead edges and drained nodes;
+// the metric slice (overrides and revived edges, disjoint: an override is of
+// an up link, merged ascending by edge id); the node list (one entry a node,
+// set bits low, cleared bits high).
+void LinkFailureSweep::Lists::append(const Expanded& x) {
+  deadList.insert(deadList.end(), x.deadEdges.begin(), x.deadEdges.end());
+  drainList.insert(drainList.end(), x.drainedNodes.begin(), x.drainedNodes.end());
+  deadOff.push_back(uint32_t(deadList.size()));
+  drainOff.push_back(uint32_t(drainList.size()));
+  maxDead = std::max(maxDead, uint32_t(x.deadEdges.size()));
+  for (size_t i = 0, j = 0; i < x.metricEdges.size() || j < x.revivedEdges.size();) {
+    const bool rev = i == x.metricEdges.size() ||
+        (j < x.revivedEdges.size() && x.revivedEdges[j] < x.metricEdges[i]);
+    metricEdge.push_back(rev ? x.revivedEdges[j] : x.metricEdges[i]);
+    metricVal.push_back(rev ? x.revivedVals[j] : x.metricVals[i]);
+    metricUp.push_back(rev ? 1 : 0);
+    ++(rev ? j : i);
+  }
+  std::map<uint32_t, uint8_t> nb;
+  for (size_t i = 0; i < x.flagNodes.size(); ++i) nb[x.flagNodes[i]] |= x.flagBits[i];
+  for (size_t i = 0; i < x.clearedNodes.size(); ++i) {
+    nb[x.clearedNodes[i]] |= uint8_t(x.clearedBits[i] << OGS_NODE_CLEAR_SHIFT);
+  }
+  for (const auto& [u, b] : nb) {
+    flagNode.push_back(u);
+    flagBits.push_back(b);
+    whatif = whatif || (b & ~uint8_t(OGS_NODE_OVERLOADED)) != 0;
+  }
+  restores = restores || !x.revivedEdges.empty() || !x.clearedNodes.empty();
+  metricOff.push_back(uint32_t(metricEdge.size()));
+  flagOff.push_back(uint32_t(flagNode.size()));
+  maxMetricList = std::max(maxMetricList, uint32_t(x.metricEdges.size() + x.revivedEdges.size()));
+  whatif = whatif || restores || !metricEdge.empty();
+}
+
+// Zero / negative link metrics (extraction-order replay) or path sums past
+// 32 bits: the packed 32-bit {dist, nh} repair does not apply, every variant
+// runs as a topology of its own (exactLaunch); so do next-hop sets of more
+// than 4 words (source degree > 128: past the variants kernel, ogs_spf_routes
+// takes up to 16). The overrides' own guards: a zero / negative weight replays
+// the extraction order, a weight that pushes max_metric x (N - 1) past the
+// 32-bit guard needs 64-bit distances -- either way topology copies.
+LinkFailureSweep::AreaDomain LinkFailureSweep::areaDomain(
+    const FlatTopology& f, const HostBatch& hb, int W, const std::vector<uint64_t>& metricVals) {
+  AreaDomain d;
+  d.exact = wideDistancesNeeded(f) || hb.hasZeroMetric || W > 4;
+  d.exactOrder = f.hasZeroMetric || f.hasWideMetric;
+  const uint64_t n = f.names.empty() ? 0 : f.names.size() - 1;
+  for (const uint64_t w : metricVals) {
+    if (w == 0 || w > 0xFFFFFFFFull) d.exact = d.exactOrder = true;
+    if (n != 0 && w > 0x7FFFFFFEull / n) d.exact = true;
+  }
+  if (!d.exact) {
+    ogs_graph shape{};  // the two fields the question reads
+    shape.max_nodes = hb.maxNodes;
+    shape.max_degree = hb.maxDegree;
+    d.needsGlobal = ogs_whatif_needs_global(&shape, 0u, W) != 0;
+  }
+  return d;
+}
+
 LinkFailureSweep::Form LinkFailureSweep::selectForm() const {
   if (exact_) return kTopologyCopies;
   if (needsGlobal_ || forceGlobal_) return kGlobalState;
-  if (maxDead_ <= kRegisterMax && drainList_.empty() && !forceBitset_ && !whatif_) {
+  if (lists_.maxDead <= kRegisterMax && lists_.drainList.empty() && !forceBitset_ &&
+      !lists_.whatif) {
     return kRegisterList;
   }
   return kEdgeBitset;  // launch() falls back to copies when the entry refuses
@@ -294,10 +356,11 @@ LinkFailureSweep::Form LinkFailureSweep::selectForm() const {
 // The lists as ogs_unit_mods slots: 4 a unit (two links, both directions) as
 // every sweep before scenarios had them, up to 8 when a list is longer.
 void LinkFailureSweep::uploadRegisterSlots() {
-  deadPer_ = int(std::max<uint32_t>(4, maxDead_));
+  deadPer_ = int(std::max<uint32_t>(4, lists_.maxDead));
   std::vector<uint32_t> slots(numVariants() * size_t(deadPer_), OGS_NODE_NONE);
   for (size_t v = 0; v < numVariants(); ++v) {
-    std::copy(deadList_.begin() + deadOff_[v], deadList_.begin() + deadOff_[v + 1],
+    std::copy(lists_.deadList.begin() + lists_.deadOff[v],
+              lists_.deadList.begin() + lists_.deadOff[v + 1],
               slots.begin() + v * size_t(deadPer_));
   }
   dDead_.upload(slots.data(), slots.size());
@@ -341,17 +404,17 @@ void LinkFailureSweep::uploadWhatifLists() {
   if (whatifUploaded_ || exact_) return;
   whatifUploaded_ = true;
   // all within 31 bits (the domain guards sent anything else to copies)
-  std::vector<uint32_t> vals(metricVal_.begin(), metricVal_.end());
+  std::vector<uint32_t> vals(lists_.metricVal.begin(), lists_.metricVal.end());
   for (size_t i = 0; i < vals.size(); ++i) {
-    if (metricUp_[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
+    if (lists_.metricUp[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
   }
-  dMetricOff_.upload(metricOff_.data(), metricOff_.size());
-  dMetricEdge_.upload(metricEdge_.data(), metricEdge_.size());
+  dMetricOff_.upload(lists_.metricOff.data(), lists_.metricOff.size());
+  dMetricEdge_.upload(lists_.metricEdge.data(), lists_.metricEdge.size());
   dMetricVal_.upload(vals.data(), vals.size());
-  if (!flagNode_.empty()) {
-    dFlagOff_.upload(flagOff_.data(), flagOff_.size());
-    dFlagNode_.upload(flagNode_.data(), flagNode_.size());
-    dFlagBits_.upload(flagBits_.data(), flagBits_.size());
+  if (!lists_.flagNode.empty()) {
+    dFlagOff_.upload(lists_.flagOff.data(), lists_.flagOff.size());
+    dFlagNode_.upload(lists_.flagNode.data(), lists_.flagNode.size());
+    dFlagBits_.upload(lists_.flagBits.data(), lists_.flagBits.size());
   }
 }
 
@@ -364,7 +427,7 @@ size_t LinkFailureSweep::globalChunkUnits(bool ownRows) const {
   const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
   const size_t E = size_t(std::max(hb_.maxEdges, 0));
   const size_t rows = ownRows ? 0 : 4 * Sn + 4 * size_t(W_) * Sn;
-  const size_t flagRow = flagNode_.empty() ? 0 : ((Sn + 3) & ~size_t(3));
+  const size_t flagRow = lists_.flagNode.empty() ? 0 : ((Sn + 3) & ~size_t(3));
   const size_t perUnit = 12 * Sn + 8 * ((E + 31) / 32) + 4 + flagRow + rows;
   constexpr size_t kBudget = (size_t(1) << 30) - 6 * 255;  // the regions' padding
   return std::max<size_t>(1, kBudget / perUnit);
@@ -379,7 +442,7 @@ void LinkFailureSweep::globalLaunch(const ogs_graph& g, const ogs_prefix_table& 
   uploadWhatifLists();
   const size_t U = numVariants(), Sn = size_t(std::max(hb_.maxNodes, 1));
   const size_t chunk = globalChunkUnits(out.dist && out.nh);
-  const bool nodes = !flagNode_.empty(), metrics = !metricEdge_.empty();
+  const bool nodes = !lists_.flagNode.empty(), metrics = !lists_.metricEdge.empty();
   for (size_t c0 = 0; c0 < U; c0 += chunk) {
     const size_t n = std::min(chunk, U - c0);
     ogs_whatif_mods mods{dDeadOff_.as<uint32_t>() + c0, dDeadList_.as<uint32_t>(),
@@ -388,7 +451,7 @@ void LinkFailureSweep::globalLaunch(const ogs_graph& g, const ogs_prefix_table& 
                          nodes ? dFlagBits_.as<uint8_t>() : nullptr,
                          metrics ? dMetricOff_.as<uint32_t>() + c0 : nullptr,
                          metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
-                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, maxMetricList_};
+                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, lists_.maxMetricList};
     ogs_route_diff d = diff;
     d.changed += c0 * words_;
     d.counts += c0 * 2;
@@ -430,74 +493,17 @@ LinkFailureSweep::LinkFailureSweep(
   if (sIt == f.id.end()) {
     throw std::invalid_argument("LinkFailureSweep: " + me_ + " is not in area " + area_);
   }
-  const bool wide = wideDistancesNeeded(f);
   table_.build(ps);
   hb_.append(f, ps, area_);
-  // zero / negative link metrics (extraction-order replay) or path sums past
-  // 32 bits: the variants kernel's packed 32-bit {dist, nh} repair does not
-  // apply, every variant runs as a topology of its own (exactLaunch)
-  exact_ = wide || hb_.hasZeroMetric;
-  exactOrder_ = f.hasZeroMetric || f.hasWideMetric;
   const uint32_t s = sIt->second;
   W_ = std::max(1, ogs_nh_words_for_degree(int(f.rowPtr[s + 1] - f.rowPtr[s])));
-  // next-hop sets of more than 4 words (source degree > 128): past the
-  // variants kernel, ogs_spf_routes takes up to 16
-  if (W_ > 4) exact_ = true;
-
-  // every scenario's dead directed edges and drained nodes, as CSR lists
-  for (const Scenario& sc : scenarios) {
-    const Expanded x = expandScenario(ls, me_, sc);
-    deadList_.insert(deadList_.end(), x.deadEdges.begin(), x.deadEdges.end());
-    drainList_.insert(drainList_.end(), x.drainedNodes.begin(), x.drainedNodes.end());
-    deadOff_.push_back(uint32_t(deadList_.size()));
-    drainOff_.push_back(uint32_t(drainList_.size()));
-    maxDead_ = std::max(maxDead_, uint32_t(x.deadEdges.size()));
-    // the unit's metric slice: overrides and revived edges (disjoint: an
-    // override is of an up link), merged ascending by edge id
-    for (size_t i = 0, j = 0; i < x.metricEdges.size() || j < x.revivedEdges.size();) {
-      const bool rev = i == x.metricEdges.size() ||
-          (j < x.revivedEdges.size() && x.revivedEdges[j] < x.metricEdges[i]);
-      metricEdge_.push_back(rev ? x.revivedEdges[j] : x.metricEdges[i]);
-      metricVal_.push_back(rev ? x.revivedVals[j] : x.metricVals[i]);
-      metricUp_.push_back(rev ? 1 : 0);
-      ++(rev ? j : i);
-    }
-    // its node list: one entry a node, set bits low, cleared bits high
-    {
-      std::map<uint32_t, uint8_t> nb;
-      for (size_t i = 0; i < x.flagNodes.size(); ++i) nb[x.flagNodes[i]] |= x.flagBits[i];
-      for (size_t i = 0; i < x.clearedNodes.size(); ++i) {
-        nb[x.clearedNodes[i]] |= uint8_t(x.clearedBits[i] << OGS_NODE_CLEAR_SHIFT);
-      }
-      for (const auto& [u, b] : nb) {
-        flagNode_.push_back(u);
-        flagBits_.push_back(b);
-      }
-    }
-    restores_ = restores_ || !x.revivedEdges.empty() || !x.clearedNodes.empty();
-    metricOff_.push_back(uint32_t(metricEdge_.size()));
-    flagOff_.push_back(uint32_t(flagNode_.size()));
-    maxMetricList_ = std::max(maxMetricList_,
-                              uint32_t(x.metricEdges.size() + x.revivedEdges.size()));
-  }
-  whatif_ = restores_ || !metricEdge_.empty() ||
-      std::any_of(flagBits_.begin(), flagBits_.end(),
-                  [](uint8_t b) { return (b & ~uint8_t(OGS_NODE_OVERLOADED)) != 0; });
-  // the overrides' own domain guards: a zero / negative weight replays the
-  // extraction order, a weight that pushes max_metric x (N - 1) past the
-  // 32-bit guard needs 64-bit distances -- either way topology copies
+  // every scenario's lists (Lists::append), then the area's domain
+  for (const Scenario& sc : scenarios) lists_.append(expandScenario(ls, me_, sc));
   {
-    const uint64_t n = f.names.empty() ? 0 : f.names.size() - 1;
-    for (const uint64_t w : metricVal_) {
-      if (w == 0 || w > 0xFFFFFFFFull) exact_ = exactOrder_ = true;
-      if (n != 0 && w > 0x7FFFFFFEull / n) exact_ = true;
-    }
-  }
-  if (!exact_) {
-    ogs_graph shape{};  // the two fields the question reads
-    shape.max_nodes = hb_.maxNodes;
-    shape.max_degree = hb_.maxDegree;
-    needsGlobal_ = ogs_whatif_needs_global(&shape, 0u, W_) != 0;
+    const AreaDomain d = areaDomain(f, hb_, W_, lists_.metricVal);
+    exact_ = d.exact;
+    exactOrder_ = d.exactOrder;
+    needsGlobal_ = d.needsGlobal;
   }
   form_ = selectForm();
 
@@ -511,13 +517,13 @@ LinkFailureSweep::LinkFailureSweep(
   dUnits_.upload(units.data(), units.size());
   dBaseUnit_.upload(&base, 1);
   if (form_ == kRegisterList) uploadRegisterSlots();
-  dDeadOff_.upload(deadOff_.data(), deadOff_.size());
-  dDeadList_.upload(deadList_.data(), deadList_.size());
-  if (!drainList_.empty()) {
-    dDrainOff_.upload(drainOff_.data(), drainOff_.size());
-    dDrainList_.upload(drainList_.data(), drainList_.size());
+  dDeadOff_.upload(lists_.deadOff.data(), lists_.deadOff.size());
+  dDeadList_.upload(lists_.deadList.data(), lists_.deadList.size());
+  if (!lists_.drainList.empty()) {
+    dDrainOff_.upload(lists_.drainOff.data(), lists_.drainOff.size());
+    dDrainList_.upload(lists_.drainList.data(), lists_.drainList.size());
   }
-  if ((whatif_ || form_ == kGlobalState) && !exact_) uploadWhatifLists();
+  if ((lists_.whatif || form_ == kGlobalState) && !exact_) uploadWhatifLists();
   {
     const std::vector<uint32_t> cls = advClasses(table_);
     dAdvClass_.upload(cls.data(), cls.size());
@@ -583,14 +589,14 @@ void LinkFailureSweep::exactLaunch(void* stream) {
       const uint32_t e0 = uint32_t(hb.edges.size()), n0 = uint32_t(hb.nodeFlags.size());
       hb.append(f, ps_, area_);
       if (t == 0) continue;
-      for (uint32_t i = deadOff_[t - 1]; i < deadOff_[t]; ++i) {
-        hb.edges[e0 + deadList_[i]] |= OGS_EDGE_DOWN;
+      for (uint32_t i = lists_.deadOff[t - 1]; i < lists_.deadOff[t]; ++i) {
+        hb.edges[e0 + lists_.deadList[i]] |= OGS_EDGE_DOWN;
       }
       // a drain, as LinkState::patchFlat encodes it: the node's flag and
       // OGS_EDGE_DST_OVERLOADED on every edge into it (the reverse of each
       // edge of its row: links are two-way)
-      for (uint32_t i = drainOff_[t - 1]; i < drainOff_[t]; ++i) {
-        const uint32_t x = drainList_[i];
+      for (uint32_t i = lists_.drainOff[t - 1]; i < lists_.drainOff[t]; ++i) {
+        const uint32_t x = lists_.drainList[i];
         hb.nodeFlags[n0 + x] |= OGS_NODE_OVERLOADED;
         for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
           const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
@@ -601,25 +607,26 @@ void LinkFailureSweep::exactLaunch(void* stream) {
       }
       // metric overrides, as LinkState::patchFlat re-encodes a moved metric,
       // and the soft-drain bits (link_state.cpp: the node's flags alone)
-      for (uint32_t i = metricOff_[t - 1]; i < metricOff_[t]; ++i) {
-        uint64_t& w = hb.edges[e0 + metricEdge_[i]];
-        w = (w & 0xFFFFFFFFull) | (uint64_t(uint32_t(metricVal_[i])) << 32);
+      for (uint32_t i = lists_.metricOff[t - 1]; i < lists_.metricOff[t]; ++i) {
+        uint64_t& w = hb.edges[e0 + lists_.metricEdge[i]];
+        w = (w & 0xFFFFFFFFull) | (uint64_t(uint32_t(lists_.metricVal[i])) << 32);
         // a revived link: up again with that weight (a dead edge stays dead)
-        const bool dead = std::binary_search(deadList_.begin() + deadOff_[t - 1],
-                                             deadList_.begin() + deadOff_[t], metricEdge_[i]);
-        if (metricUp_[i] && !dead) w &= ~uint64_t(OGS_EDGE_DOWN);
-        hb.maxMetric = std::max(hb.maxMetric, metricVal_[i]);
-        hb.hasZeroMetric |= metricVal_[i] == 0;
+        const bool dead = std::binary_search(lists_.deadList.begin() + lists_.deadOff[t - 1],
+                                             lists_.deadList.begin() + lists_.deadOff[t],
+                                             lists_.metricEdge[i]);
+        if (lists_.metricUp[i] && !dead) w &= ~uint64_t(OGS_EDGE_DOWN);
+        hb.maxMetric = std::max(hb.maxMetric, lists_.metricVal[i]);
+        hb.hasZeroMetric |= lists_.metricVal[i] == 0;
       }
       // flag bits: cleared first, then set -- an undrain is the mirror image
       // of the drain above (the flag, and OGS_EDGE_DST_OVERLOADED off every
       // edge into the node)
-      for (uint32_t i = flagOff_[t - 1]; i < flagOff_[t]; ++i) {
-        const uint32_t x = flagNode_[i];
-        const uint8_t clr = uint8_t((flagBits_[i] >> OGS_NODE_CLEAR_SHIFT) & 0x7u);
+      for (uint32_t i = lists_.flagOff[t - 1]; i < lists_.flagOff[t]; ++i) {
+        const uint32_t x = lists_.flagNode[i];
+        const uint8_t clr = uint8_t((lists_.flagBits[i] >> OGS_NODE_CLEAR_SHIFT) & 0x7u);
         uint8_t& nf = hb.nodeFlags[n0 + x];
         const bool was = (nf & OGS_NODE_OVERLOADED) != 0;
-        nf = uint8_t((nf & ~clr) | (flagBits_[i] & 0x0Fu));
+        nf = uint8_t((nf & ~clr) | (lists_.flagBits[i] & 0x0Fu));
         if (!was || (nf & OGS_NODE_OVERLOADED)) continue;
         for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
           const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
@@ -757,8 +764,8 @@ void LinkFailureSweep::launch(void* stream, bool records) {
   uint32_t fl = flags();
   if (mode_ != kFull) fl |= OGS_F_INCREMENTAL;
   if (changedOnly) fl |= OGS_F_CHANGED_ONLY;
-  // (restores_ implies whatif_: only the two what-if entries below see the flag)
-  if (restores_) fl |= OGS_F_RESTORE;
+  // (lists_.restores implies lists_.whatif: only the two what-if entries below see the flag)
+  if (lists_.restores) fl |= OGS_F_RESTORE;
   if (form_ == kGlobalState) {
     globalLaunch(g, pt, diff, fl, out, stream);
   } else if (form_ == kRegisterList) {
@@ -769,15 +776,15 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     ogsCheck(ogs_spf_routes_variants(&g, &pt, dUnits_.as<ogs_unit>(), int32_t(numVariants()),
                                      &mods, &diff, fl, W_, &out, stream),
              "ogs_spf_routes_variants");
-  } else if (whatif_) {
-    const bool nodes = !flagNode_.empty(), metrics = !metricEdge_.empty();
+  } else if (lists_.whatif) {
+    const bool nodes = !lists_.flagNode.empty(), metrics = !lists_.metricEdge.empty();
     ogs_whatif_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
                          nodes ? dFlagOff_.as<uint32_t>() : nullptr,
                          nodes ? dFlagNode_.as<uint32_t>() : nullptr,
                          nodes ? dFlagBits_.as<uint8_t>() : nullptr,
                          metrics ? dMetricOff_.as<uint32_t>() : nullptr,
                          metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
-                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, maxMetricList_};
+                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, lists_.maxMetricList};
     const int rc = ogs_spf_routes_whatif(&g, &pt, dUnits_.as<ogs_unit>(),
                                          int32_t(numVariants()), &mods, &diff, fl, W_, &out,
                                          stream);
@@ -789,7 +796,7 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     }
     ogsCheck(rc, "ogs_spf_routes_whatif");
   } else {
-    const bool drains = !drainList_.empty();
+    const bool drains = !lists_.drainList.empty();
     ogs_scenario_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
                            drains ? dDrainOff_.as<uint32_t>() : nullptr,
                            drains ? dDrainList_.as<uint32_t>() : nullptr};
@@ -1101,6 +1108,12 @@ DecisionRouteUpdate updateOf(const FlatTopology& f, uint32_t rb, const std::stri
 }
 
 }  // namespace
+
+DecisionRouteUpdate materializeUpdate(const FlatTopology& f, const std::string& me,
+                                      const PrefixHostTable& pt, const ChangeRecords& c,
+                                      size_t v, bool v4OverV6) {
+  return updateOf(f, f.rowPtr[f.id.at(me)], me, pt, c, v, v4OverV6);
+}
 
 std::vector<DecisionRouteUpdate> materializeUpdates(const FlatTopology& f, const std::string& me,
                                                     const PrefixHostTable& pt,

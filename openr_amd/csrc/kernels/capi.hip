@@ -576,6 +576,40 @@ int ogs_spf_routes_whatif_global(const ogs_graph* graph,
   return e == hipSuccess ? OGS_OK : hipFail(e, "global what-if launch");
 }
 
+int ogs_spf_routes_whatif_pairs(const ogs_graph* graph,
+                                const ogs_prefix_table* prefixes,
+                                const ogs_unit* units, int32_t n_units,
+                                const ogs_whatif_pairs* pairs,
+                                const ogs_whatif_mods* mods,
+                                ogs_route_diff* diff, uint32_t flags,
+                                int32_t nh_words, ogs_spf_out* out, void* stream) {
+  bool done = false;
+  const int rc0 = check_whatif_args(graph, prefixes, units, n_units, mods, diff, flags, nh_words,
+                                    out, &done);
+  if (done) return rc0;
+  if (!pairs || !pairs->base || !pairs->scenario) {
+    return fail(OGS_E_INVALID, "pairs, base or scenario is NULL");
+  }
+  if (pairs->n_bases <= 0 || pairs->n_scenarios < 0) {
+    return fail(OGS_E_INVALID, "pairs: n_bases <= 0 or n_scenarios < 0");
+  }
+  int unsupported = 0;
+  hipError_t e = ogs::launch_whatif_pairs(*graph, *prefixes, units, n_units, *pairs, *mods, diff,
+                                          flags, nh_words, *out,
+                                          static_cast<hipStream_t>(stream), &unsupported);
+  if (unsupported == 1) {
+    return fail(OGS_E_UNSUPPORTED,
+                "what-if lists need the large-topology path (edge_src, nh_words <= 4, "
+                "32-bit distances)");
+  }
+  if (unsupported) {
+    return fail(OGS_E_UNSUPPORTED,
+                "what-if pairs run in the base SPF's repair only: OGS_F_INCREMENTAL, nh_words 1, "
+                "max_nodes <= 65535, bitsets, flag row and metric slice within the LDS budget");
+  }
+  return e == hipSuccess ? OGS_OK : hipFail(e, "what-if pairs launch");
+}
+
 int ogs_whatif_needs_global(const ogs_graph* graph, uint32_t flags, int32_t nh_words) {
   if (!graph || !ogs::whatif_global_takes(*graph, flags, nh_words)) return 0;
   return ogs::frontier_fits(*graph, flags, nh_words) ? 0 : 1;
@@ -832,6 +866,16 @@ int ogs_ctx_spf_routes_whatif(ogs_ctx* ctx, const ogs_graph* graph,
                               ogs_spf_out* out, void* stream) {
   OGS_CTX_CALL(ctx, ogs_spf_routes_whatif(graph, prefixes, units, n_units, mods, diff, flags,
                                           nh_words, out, stream));
+}
+
+int ogs_ctx_spf_routes_whatif_pairs(ogs_ctx* ctx, const ogs_graph* graph,
+                                    const ogs_prefix_table* prefixes, const ogs_unit* units,
+                                    int32_t n_units, const ogs_whatif_pairs* pairs,
+                                    const ogs_whatif_mods* mods, ogs_route_diff* diff,
+                                    uint32_t flags, int32_t nh_words, ogs_spf_out* out,
+                                    void* stream) {
+  OGS_CTX_CALL(ctx, ogs_spf_routes_whatif_pairs(graph, prefixes, units, n_units, pairs, mods, diff,
+                                                flags, nh_words, out, stream));
 }
 
 int ogs_ctx_ksp_paths(ogs_ctx* ctx, const ogs_graph* graph, const ogs_path_unit* units,

@@ -63,6 +63,13 @@ hipError_t launch_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
                          const ogs_whatif_mods& mods, ogs_route_diff* diff,
                          uint32_t flags, int W, const ogs_spf_out& out,
                          hipStream_t stream, int* unsupported);
+// ogs_spf_routes_whatif_pairs: the repair only. *unsupported: 1 as
+// launch_whatif, 2 the repair cannot take the call
+hipError_t launch_whatif_pairs(const ogs_graph& g, const ogs_prefix_table& pt,
+                               const ogs_unit* units, int nUnits,
+                               const ogs_whatif_pairs& pairs, const ogs_whatif_mods& mods,
+                               ogs_route_diff* diff, uint32_t flags, int W,
+                               const ogs_spf_out& out, hipStream_t stream, int* unsupported);
 // route_multiarea.hip
 hipError_t launch_routes_multiarea(const ogs_graph& g, const ogs_prefix_table& pt,
                                    const ogs_area_table& at,
@@ -203,6 +210,11 @@ hipError_t launch_whatif_repair(const ogs_graph& g, const ogs_prefix_table& pt,
                                 uint32_t flags, const ogs_spf_out& out,
                                 const ogs_whatif_mods& mods, ogs_route_diff* diff,
                                 void* scratch, hipStream_t stream);
+hipError_t launch_whatif_pairs_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                      const uint32_t* key, const ogs_unit* units, int n,
+                                      uint32_t flags, const ogs_spf_out& out,
+                                      const ogs_whatif_mods& mods, const ogs_whatif_pairs& pairs,
+                                      const ogs_route_diff& diff, hipStream_t stream);
 hipError_t launch_frontier_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
                                   const uint32_t* key, const ogs_unit* units, int n,
                                   uint32_t flags, int W, const ogs_spf_out& out,

@@ -313,6 +313,43 @@ hipError_t launch_whatif(const ogs_graph& g, const ogs_prefix_table& pt,
                                 stream);
 }
 
+// ogs_spf_routes_whatif_pairs: launch_whatif's preamble, the repair only (a
+// unit's base and lists are rows of the caller's arrays; no full form).
+hipError_t launch_whatif_pairs(const ogs_graph& g, const ogs_prefix_table& pt,
+                               const ogs_unit* units, int nUnits,
+                               const ogs_whatif_pairs& pairs, const ogs_whatif_mods& mods,
+                               ogs_route_diff* diff, uint32_t flags, int W,
+                               const ogs_spf_out& out, hipStream_t stream, int* unsupported) {
+  if (!g.edge_src || (flags & OGS_F_WIDE_METRIC) || !frontier_fits(g, flags, W) ||
+      (W != 1 && W != 2 && W != 4)) {
+    *unsupported = 1;
+    return hipSuccess;
+  }
+  const bool nodes = mods.node_off != nullptr;
+  const uint32_t maxMetric = mods.metric_off ? mods.max_metric_per_unit : 0u;
+  if (!whatif_repair_fits(g, flags, W, diff, nodes, maxMetric)) {
+    *unsupported = 2;
+    return hipSuccess;
+  }
+  ogs_whatif_mods m = mods;
+  m.max_metric_per_unit = maxMetric;
+  const size_t Sp = size_t(pt.max_prefixes);
+  void* ws = nullptr;
+  hipError_t e = workspace(round256(size_t(g.num_topos) * Sp * 4), stream, &ws);
+  if (e != hipSuccess) return e;
+  uint32_t* key = static_cast<uint32_t*>(ws);
+  e = hipMemsetAsync(diff->changed, 0, size_t(nUnits) * ((Sp + 31) / 32) * 4, stream);
+  if (e != hipSuccess) return e;
+  if (Sp > 0) {
+    hipLaunchKernelGGL(pfx_key_kernel, dim3(unsigned((Sp + kBlock - 1) / kBlock),
+                                            unsigned(g.num_topos)),
+                       dim3(kBlock), 0, stream, pt, g.num_topos, key);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return launch_whatif_pairs_repair(g, pt, key, units, nUnits, flags, out, m, pairs, *diff, stream);
+}
+
 // Large shared topologies with a prefix table: key fold, then either the
 // fused frontier SPF + stream launch (route_stream 2), or an SPF launch
 // (frontier / multi-source sweep) and a route-stream launch (route_stream 1).

@@ -1591,6 +1591,45 @@ __global__ __launch_bounds__(kBlock) void spf_whatif_repair_kernel(
 #include "spf_repair_body.h"
 }
 
+// ogs_spf_routes_whatif_pairs: the what-if repair over (source, scenario)
+// pairs. Unit u writes row u of every output; its base is row pairs.base[u] of
+// the diff's base arrays (S_n / S_p words a row) and its lists are row
+// pairs.scenario[u] of the mods' offset arrays. The statements read
+// `mods.*_off[u]` and `diff.base_*[v]`, so the unit gets copies of both whose
+// pointers are moved to its rows: the statements and every kernel above stay
+// as they are. A pair index out of range is refused before anything is
+// indexed. No descendant rows (they are per source): A grows by list rounds.
+template <bool CHANGED_ONLY, bool NODES, typename Mods = ogs_whatif_mods>
+__global__ __launch_bounds__(kBlock) void spf_whatif_pairs_kernel(
+    ogs_graph g, ogs_prefix_table pt, const uint32_t* __restrict__ key,
+    const ogs_unit* __restrict__ units, uint32_t flags, uint32_t* __restrict__ oDist,
+    uint32_t* __restrict__ oNh, ogs_spf_out out, Mods unitMods, ogs_route_diff unitDiff,
+    ogs_whatif_pairs pairs) {
+  constexpr bool WHATIF = std::is_same_v<Mods, ogs_whatif_mods>;
+  static_assert(WHATIF, "the pairs repair takes ogs_whatif_mods");
+  constexpr bool LIST = WHATIF, DRAINS = NODES;
+  const uint32_t pairUnit = blockIdx.x;
+  const uint32_t baseRow = pairs.base[pairUnit], listRow = pairs.scenario[pairUnit];
+  if (baseRow >= uint32_t(pairs.n_bases) || listRow >= uint32_t(pairs.n_scenarios)) {
+    if (threadIdx.x < 2) unitDiff.counts[size_t(pairUnit) * 2 + threadIdx.x] = OGS_WHATIF_REFUSED;
+    return;
+  }
+  // (the offsets are read at [unit] and [unit + 1]: row listRow of the arrays)
+  const ptrdiff_t rowShift = ptrdiff_t(listRow) - ptrdiff_t(pairUnit);
+  Mods mods = unitMods;
+  mods.dead_off += rowShift;
+  if constexpr (NODES) mods.node_off += rowShift;
+  if (mods.metric_off) mods.metric_off += rowShift;
+  ogs_route_diff diff = unitDiff;
+  diff.base_dist += size_t(baseRow) * uint32_t(g.max_nodes);
+  diff.base_nh += size_t(baseRow) * uint32_t(g.max_nodes);
+  diff.base_meta += size_t(baseRow) * uint32_t(pt.max_prefixes);
+  diff.base_metric += size_t(baseRow) * uint32_t(pt.max_prefixes);
+  diff.base_mask += size_t(baseRow) * uint32_t(pt.max_prefixes);
+  const uint32_t* const desc = nullptr;
+#include "spf_repair_body.h"
+}
+
 // The base's tight-DAG descendant rows for a repair launch (every unit shares
 // topology, source and base SPF: units[0] / diff->base_dist): from the
 // caller's cache when it holds them, else built (into the cache when given,
@@ -1683,6 +1722,25 @@ hipError_t launch_whatif_repair(const ogs_graph& g, const ogs_prefix_table& pt,
                         flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
                         static_cast<uint32_t*>(out.dist), out.nh, out, mods, *diff,
                         static_cast<const uint32_t*>(desc));
+}
+
+// ogs_spf_routes_whatif_pairs; call when whatif_repair_fits(). One workgroup
+// per pair, no descendant rows, no workspace beyond the keys.
+hipError_t launch_whatif_pairs_repair(const ogs_graph& g, const ogs_prefix_table& pt,
+                                      const uint32_t* key, const ogs_unit* units, int n,
+                                      uint32_t flags, const ogs_spf_out& out,
+                                      const ogs_whatif_mods& mods, const ogs_whatif_pairs& pairs,
+                                      const ogs_route_diff& diff, hipStream_t stream) {
+  const bool nodes = mods.node_off != nullptr;
+  const uint32_t lds = whatif_lds_bytes(g, nodes, mods.max_metric_per_unit);
+  const bool changedOnly = (flags & OGS_F_CHANGED_ONLY) != 0;
+  auto k = changedOnly ? (nodes ? spf_whatif_pairs_kernel<true, true>
+                                : spf_whatif_pairs_kernel<true, false>)
+                       : (nodes ? spf_whatif_pairs_kernel<false, true>
+                                : spf_whatif_pairs_kernel<false, false>);
+  return launch_dyn_lds(k, dim3(n), dim3(kBlock), lds, stream, g, pt, key, units,
+                        flags | ((opts().routeStoreNt & 1) ? kFlagNtStores : 0u),
+                        static_cast<uint32_t*>(out.dist), out.nh, out, mods, diff, pairs);
 }
 
 // ogs_spf_routes_variants with OGS_F_INCREMENTAL (W = 1); false when the

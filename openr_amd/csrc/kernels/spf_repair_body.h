@@ -1,8 +1,9 @@
 // spf_repair_body.h -- the statements of the variant repair, one body for
 // the kernels spf_frontier.hip defines around it (spf_variant_repair_kernel,
-// spf_whatif_repair_kernel). Included INSIDE a kernel definition, so each
-// kernel compiles the statements against its own parameters: the instantiations
-// that existed before the what-if form keep their code generation. A shared
+// spf_whatif_repair_kernel, spf_whatif_pairs_kernel). Included INSIDE a
+// kernel definition, so each kernel compiles the statements against its own
+// parameters: the instantiations that existed before the what-if form keep
+// their code generation. A shared
 // __forceinline__ template body was tried first, with the kernel arguments
 // passed by reference and then by value: both times
 // spf_variant_repair_kernel<false, true, false> and <false, false, false>

@@ -2358,6 +2358,79 @@ PYBIND11_MODULE(_decision, m) {
   m.attr("kTopologyCopies") = int(LinkFailureSweep::kTopologyCopies);
   m.attr("kGlobalState") = int(LinkFailureSweep::kGlobalState);
 
+  // Network-wide what-if sweep: every source's route diff per scenario
+  // (scenarios as for LinkFailureSweep). network_whatif_plan needs no device:
+  // {"batched": [source index], "fallback": [...], "pairs": [(source index,
+  // scenario)], "sourceDown": [...], "chunks": [unit boundary], "impactChunks":
+  // [...], "unitBytes", "impactUnitBytes"}.
+  m.def("network_whatif_plan",
+        [toScenario](const LinkState& ls, const PrefixState& ps,
+                     const std::vector<std::string>& sources,
+                     const std::vector<py::dict>& scenarios, size_t chunkBytes) {
+          std::vector<LinkFailureSweep::Scenario> scs;
+          for (const auto& d : scenarios) scs.push_back(toScenario(d));
+          const NetworkWhatifPlan p = network_whatif_plan(ls, ps, sources, scs, chunkBytes);
+          py::dict out;
+          out["batched"] = p.batched;
+          out["fallback"] = p.fallback;
+          out["pairs"] = p.pairs;
+          out["sourceDown"] = p.sourceDown;
+          out["chunks"] = p.chunks;
+          out["impactChunks"] = p.impactChunks;
+          out["unitBytes"] = p.unitBytes;
+          out["impactUnitBytes"] = p.impactUnitBytes;
+          return out;
+        },
+        py::arg("linkState"), py::arg("prefixState"), py::arg("sources"), py::arg("scenarios"),
+        py::arg("chunkBytes") = size_t(1) << 30);
+  py::class_<NetworkWhatifSweep>(m, "NetworkWhatifSweep")
+      .def(py::init([toScenario](const LinkState& ls, const PrefixState& ps,
+                                 const std::vector<std::string>& sources,
+                                 const std::vector<py::dict>& scenarios, bool enableV4,
+                                 bool brs) {
+             std::vector<LinkFailureSweep::Scenario> scs;
+             for (const auto& d : scenarios) scs.push_back(toScenario(d));
+             return std::make_unique<NetworkWhatifSweep>(ls, ps, sources, scs, enableV4, brs);
+           }),
+           py::arg("linkState"), py::arg("prefixState"), py::arg("sources"),
+           py::arg("scenarios"), py::arg("enableV4"),
+           py::arg("enableBestRouteSelection") = false, py::keep_alive<1, 2>(),
+           py::keep_alive<1, 3>())
+      .def("launch", [](NetworkWhatifSweep& s, uintptr_t stream, bool records) {
+             py::gil_scoped_release nogil;
+             s.launch(reinterpret_cast<void*>(stream), records);
+           }, py::arg("stream") = 0, py::arg("records") = true)
+      .def("fetchImpact", [](NetworkWhatifSweep& s, uintptr_t stream) {
+             s.fetchImpact(reinterpret_cast<void*>(stream));
+           }, py::arg("stream") = 0)
+      .def("fetchUpdates", [](NetworkWhatifSweep& s, uintptr_t stream) {
+             s.fetchUpdates(reinterpret_cast<void*>(stream));
+           }, py::arg("stream") = 0)
+      .def("numSources", &NetworkWhatifSweep::numSources)
+      .def("numScenarios", &NetworkWhatifSweep::numScenarios)
+      .def("batchedSources", &NetworkWhatifSweep::batchedSources)
+      .def("numChunks", &NetworkWhatifSweep::numChunks, py::arg("records") = true)
+      .def("state", [](const NetworkWhatifSweep& s, size_t src, size_t k) {
+             return int(s.state(src, k));
+           })
+      .def("counts", &NetworkWhatifSweep::counts)
+      .def("affectedSources", &NetworkWhatifSweep::affectedSources)
+      .def("changedPrefixes", &NetworkWhatifSweep::changedPrefixes)
+      .def("routeUpdate", [](const NetworkWhatifSweep& s, size_t src, size_t k) {
+             return fromUpdate(s.routeUpdate(src, k));
+           })
+      .def("updatedCanonical", [](const NetworkWhatifSweep& s, size_t src, size_t k) {
+             DecisionRouteDb db = s.baseRouteDb(src);
+             db.update(s.routeUpdate(src, k));
+             return py::bytes(canonical(db));
+           })
+      .def("baseCanonical", [](const NetworkWhatifSweep& s, size_t src) {
+             return py::bytes(canonical(s.baseRouteDb(src)));
+           })
+      .def("setChunkBytes", &NetworkWhatifSweep::setChunkBytes, py::arg("bytes"));
+  m.attr("kComputed") = int(NetworkWhatifSweep::kComputed);
+  m.attr("kSourceDown") = int(NetworkWhatifSweep::kSourceDown);
+
   py::class_<VariantRunner>(m, "VariantRunner")
       .def(py::init<bool, bool>(), py::arg("enableV4") = true,
            py::arg("enableBestRouteSelection") = false)
@@ -2417,6 +2490,47 @@ PYBIND11_MODULE(_decision, m) {
       .def("ksp_dests", &C5Runner::kspDests)
       .def("routes_digest", &C5Runner::routesDigest, py::arg("stream") = 0)
       .def("shape", &C5Runner::shape);
+
+  // a HostBatch as numpy arrays and its shape
+  auto hostBatchDict = [](const HostBatch& h) {
+    py::dict d;
+    d["node_base"] = npcopy(h.nodeBase);
+    d["topo_desc"] = npcopy(h.topoDesc);
+    d["row_ptr"] = npcopy(h.rowPtr);
+    d["edges"] = npcopy(h.edges);
+    d["edge_src"] = npcopy(h.edgeSrc);
+    d["node_flags"] = npcopy(h.nodeFlags);
+    d["pfx_base"] = npcopy(h.pfxBase);
+    d["adv_off"] = npcopy(h.advOff);
+    d["adv_node"] = npcopy(h.advNode);
+    d["adv_metrics"] = npcopy(h.advMetrics);
+    d["adv_min_nh"] = npcopy(h.advMinNh);
+    d["pfx_flags"] = npcopy(h.pfxFlags);
+    std::vector<uint16_t> slots;
+    std::vector<uint32_t> slotEdges;
+    int slotDegree = 0;
+    d["slot_stride"] = h.slotOrder(slots, &slotEdges, &slotDegree);
+    d["slot_node"] = npcopy(slots);
+    d["slot_edges"] = npcopy(slotEdges);
+    d["slot_degree"] = slotDegree;
+    d["max_nodes"] = h.maxNodes;
+    d["max_edges"] = h.maxEdges;
+    d["max_prefixes"] = h.maxPrefixes;
+    d["max_advertisements"] = h.maxAdvs;
+    d["max_degree"] = h.maxDegree;
+    d["num_topos"] = int(h.nodeBase.size() - 1);
+    return d;
+  };
+  // one area of Python-built LinkState / PrefixState objects as the HBM image
+  // the C-ABI entries consume (host_arrays' keys but units / nh_words / flags)
+  // + "names": node id -> name
+  m.def("area_host_arrays", [hostBatchDict](const LinkState& ls, const PrefixState& ps) {
+    HostBatch h;
+    h.append(ls.flat(), ps, ls.getArea());
+    py::dict d = hostBatchDict(h);
+    d["names"] = ls.flat().names;
+    return d;
+  }, py::arg("linkState"), py::arg("prefixState"));
 
   py::class_<BatchRunner>(m, "BatchRunner")
       .def(py::init<bool, bool, bool>(), py::arg("enableV4") = true,
@@ -2486,41 +2600,16 @@ PYBIND11_MODULE(_decision, m) {
            "hand the wave kernel the per-position edge image (default on)")
       .def("nh_words", &BatchRunner::nhWords)
       .def("wide", &BatchRunner::wide)
-      .def("host_arrays", [](const BatchRunner& b) {
+      .def("host_arrays", [hostBatchDict](const BatchRunner& b) {
         // the exact HBM image the kernel consumes (bench.py uploads it)
         const HostBatch& h = b.host();
-        py::dict d;
-        d["node_base"] = npcopy(h.nodeBase);
-        d["topo_desc"] = npcopy(h.topoDesc);
-        d["row_ptr"] = npcopy(h.rowPtr);
-        d["edges"] = npcopy(h.edges);
-        d["edge_src"] = npcopy(h.edgeSrc);
-        d["node_flags"] = npcopy(h.nodeFlags);
-        d["pfx_base"] = npcopy(h.pfxBase);
-        d["adv_off"] = npcopy(h.advOff);
-        d["adv_node"] = npcopy(h.advNode);
-        d["adv_metrics"] = npcopy(h.advMetrics);
-        d["adv_min_nh"] = npcopy(h.advMinNh);
-        d["pfx_flags"] = npcopy(h.pfxFlags);
-        std::vector<uint16_t> slots;
-        std::vector<uint32_t> slotEdges;
-        int slotDegree = 0;
-        d["slot_stride"] = h.slotOrder(slots, &slotEdges, &slotDegree);
-        d["slot_node"] = npcopy(slots);
-        d["slot_edges"] = npcopy(slotEdges);
-        d["slot_degree"] = slotDegree;
+        py::dict d = hostBatchDict(h);
         std::vector<uint32_t> u;
         for (const auto& x : b.units()) {
           u.push_back(x.topo);
           u.push_back(x.src);
         }
         d["units"] = npcopy(u);
-        d["max_nodes"] = h.maxNodes;
-        d["max_edges"] = h.maxEdges;
-        d["max_prefixes"] = h.maxPrefixes;
-        d["max_advertisements"] = h.maxAdvs;
-        d["max_degree"] = h.maxDegree;
-        d["num_topos"] = int(h.nodeBase.size() - 1);
         d["nh_words"] = b.nhWords();
         d["flags"] = b.flags();
         return d;

@@ -52,7 +52,21 @@ label routes too and the sample is compared with MPLS included
 SPF rows the launch wrote (4 (1 + W) S_n per scenario) and the changed-node
 total.
 
+With --sources N the question is network-wide: the first N nodes are sources
+and every (source, scenario) pair of a set is computed, on the C4 WAN, sets
+from a .. g (default "ea"). Per set, from one process:
+  - NetworkWhatifSweep: construction, then launch + fetchUpdates (records) and
+    launch(records=False) + fetchImpact, each the median of 3 after a warm-up;
+  - the loop of one LinkFailureSweep per source over the same scenarios (mode
+    kChangedOnly): construction + base run summed, and launch + fetchUpdates
+    summed (each sweep's second launch, so its descendant rows are cached);
+    every pair's counts must equal the batch's;
+  - the oracle's own loop on a sample of 64 pairs (8 sources x 8 scenarios), ms
+    per pair; the sample's updates, counts and updated RouteDbs must equal the
+    batch's.
+
   python tools/whatif_sweep.py [--nodes 2000] [--sample 64] [--sets abcdefg] [--labels]
+  python tools/whatif_sweep.py --sources 64 [--sets ea]
   python tools/whatif_sweep.py --g1 [--nodes 20000] [--sample 64] [--sets hijkl]
   python tools/whatif_sweep.py --restore [--g1] [--sets mnos | pqr]"""
 import argparse
@@ -89,6 +103,81 @@ def fresh_world(base):
     return FreshWorld
 
 
+def network_rows(args, M, O, W, w, ls, ps, sets):
+    """--sources N: the batched sweep beside the per-source loop and the oracle"""
+    from test_gpu_network_whatif import Source
+    sources = sorted(w.adjdbs, key=int)[:args.sources]
+    out = []
+    for label, scs, _, _ in sets:
+        t0 = time.perf_counter()
+        net = M.NetworkWhatifSweep(ls, ps, sources, scs, True, False)
+        build_ms = (time.perf_counter() - t0) * 1e3
+        rec, imp = [], []
+        for i in range(4):
+            t0 = time.perf_counter()
+            net.launch()
+            net.fetchUpdates()
+            rec.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            net.launch(records=False)
+            net.fetchImpact()
+            imp.append((time.perf_counter() - t0) * 1e3)
+        net.launch()
+        net.fetchUpdates()
+        S, K = len(sources), len(scs)
+        live = [[k for k in range(K) if net.state(s, k) == M.kComputed] for s in range(S)]
+        pairs = sum(len(l) for l in live)
+        changed = sum(sum(net.counts(s, k)) for s in range(S) for k in live[s])
+        affected = sum(len(net.affectedSources(k)) for k in range(K))
+        # the per-source loop: the same pairs, one LinkFailureSweep a source
+        loop_build, loop_run = 0.0, 0.0
+        for s, me in enumerate(sources):
+            t0 = time.perf_counter()
+            sw = M.LinkFailureSweep(me, ls, ps, [scs[k] for k in live[s]], True, False)
+            sw.setMode(2)
+            sw.launch()  # the first launch runs the base and builds its descendant rows
+            sw.fetchUpdates()
+            loop_build += (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            sw.launch()
+            sw.fetchUpdates()
+            loop_run += (time.perf_counter() - t0) * 1e3
+            for v, k in enumerate(live[s]):
+                assert tuple(sw.counts(v)) == tuple(net.counts(s, k)), (label, me, k)
+            del sw
+        # the oracle on 8 sources x 8 scenarios
+        n = max(1, int(args.sample ** 0.5))
+        cpu, checked = [], 0
+        for s in sorted({i * S // n for i in range(n)}):
+            oracle = W.Oracle(O, w, sources[s])
+            ks = [k for k in sorted({i * K // n for i in range(n)}) if k in set(live[s])]
+            t0 = time.perf_counter()
+            for k in ks:
+                oracle.answer(scs[k], canonical=False)
+            cpu.append((time.perf_counter() - t0) * 1e3 / max(1, len(ks)))
+            W.check_sweep(Source(net, s), [oracle.answer(scs[k]) for k in ks], (label, s), ks)
+            checked += len(ks)
+        row = dict(set=label, sources=S, scenarios=K, pairs=pairs, batched=net.batchedSources(),
+                   chunks=net.numChunks(), impact_chunks=net.numChunks(False),
+                   construct_ms=build_ms, batched_records_ms=median(rec[1:]),
+                   batched_impact_ms=median(imp[1:]), loop_construct_base_ms=loop_build,
+                   loop_launch_fetch_ms=loop_run, ratio_loop_over_batched=loop_run / median(rec[1:]),
+                   changed_routes=changed, affected_pairs=affected,
+                   cpu_ms_per_pair=median(cpu), sample=checked)
+        out.append(row)
+        print(f"  {label:22s} {S} sources x {K} scenarios = {pairs} pairs, "
+              f"{row['batched']} batched, {row['chunks']} chunk(s)\n"
+              f"    batched: construct {build_ms:9.1f} ms, launch+fetchUpdates "
+              f"{row['batched_records_ms']:9.2f} ms, impact only {row['batched_impact_ms']:9.2f} ms\n"
+              f"    per-source loop: construct+base {loop_build:9.1f} ms, launch+fetchUpdates "
+              f"{loop_run:9.2f} ms summed over {S} sweeps (every pair's counts equal)\n"
+              f"    loop / batched = {row['ratio_loop_over_batched']:.2f}x; changed routes {changed}, "
+              f"affected (source, scenario) pairs {affected}\n"
+              f"    oracle loop {row['cpu_ms_per_pair']:.3f} ms/pair x {pairs} = "
+              f"{row['cpu_ms_per_pair'] * pairs / 1e3:.1f} s (extrapolated from {checked}; sample equal)")
+    print(json.dumps(dict(workload="c4_whatif_network", nodes=len(w.adjdbs), rows=out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=0, help="override C4's node count (smoke runs)")
@@ -103,7 +192,14 @@ def main():
     ap.add_argument("--labels", action="store_true",
                     help="node label 100000 + id on every node; each set also with "
                          "enableNodeSegmentLabel, the sample compared with MPLS included")
+    ap.add_argument("--sources", type=int, default=0,
+                    help="network-wide: the first N nodes as sources (NetworkWhatifSweep beside "
+                         "the per-source loop and the oracle)")
     args = ap.parse_args()
+    if args.sources and (args.g1 or args.restore or args.labels):
+        ap.error("--sources runs on the plain C4 WAN")
+    if args.sets is None and args.sources:
+        args.sets = "ea"
     if args.sets is None:
         if args.restore:
             args.sets = "pqr" if args.g1 else "mnos"
@@ -196,6 +292,9 @@ def main():
           f"{w.directed_edges()} directed edges, "
           f"source {me}, mode kChangedOnly unless a row says kFull")
     als, ls, ps = w.load(M, me)
+    if args.sources:
+        sets.sort(key=lambda s: args.sets.index(s[0][0]))
+        return network_rows(args, M, O, W, w, ls, ps, sets)
     oracle = (WL.LabelOracle if args.labels else W.Oracle)(O, w, me)
     base, weight, far = {}, {}, {}  # the exit-only rule's inputs: the G1 rows alone
     if args.g1:
