@@ -1181,6 +1181,64 @@ struct ChangeRecords {
   size_t total{0};
   int W{1};
 };
+// Exclusive scan of per-unit change counts (Per a unit: 2, update and delete,
+// or 1 for label rows) into offsets[units + 1]; returns the total. A unit
+// whose first count is OGS_WHATIF_REFUSED wrote nothing and adds nothing.
+// std::length_error when `before` (records already held) + the total passes
+// 2^32 - 1.
+template <size_t Per>
+uint64_t scanChangeCounts(const uint32_t* counts, size_t units, std::vector<uint32_t>& offsets,
+                          uint64_t before = 0) {
+  offsets.resize(units + 1);
+  offsets[0] = 0;
+  uint64_t total = 0;
+  for (size_t u = 0; u < units; ++u, counts += Per) {
+    uint64_t unit = 0;
+    for (size_t i = 0; i < Per; ++i) unit += counts[i];
+    if (counts[0] != OGS_WHATIF_REFUSED) total += unit;
+    offsets[u + 1] = uint32_t(total);
+  }
+  if (before + total > 0xFFFFFFFFull) throw std::length_error("what-if sweep: > 2^32 changes");
+  return total;
+}
+// counts -> offsets -> ogs_route_changes_gather -> compact records on the
+// host, for the units of one sweep, gathered in one chunk or appended chunk by
+// chunk in unit order (W = 1 only: mask[w * total + i] does not append).
+struct CompactChanges {
+  void reset(size_t units, int W);  // start over
+  // Units [u0, u0 + n) with their host counts (2 a unit), the chunk's bitmap
+  // and dense record rows on the device. Enqueues on `stream`: the caller syncs
+  // it before the next gather and before reading view(). std::logic_error for
+  // a chunk out of order, or a second one at W > 1.
+  void gather(size_t u0, size_t n, const uint32_t* counts, const uint32_t* dChanged,
+              const ogs_spf_out& rec, size_t Sp, void* stream);
+  ChangeRecords view() const;
+  std::vector<uint32_t> offsets, prefix, meta, metric, mask;
+  DeviceBuffer dOffsets, cPrefix, cMeta, cMetric, cMask;
+
+ private:
+  int W_{1};
+  size_t done_{0};               // units gathered so far
+  std::vector<uint32_t> local_;  // the chunk's own offsets (uploaded)
+};
+// The unicast routes of one unit's dense record rows, in table order, into
+// db: prefix p from meta[p], metric[p] (32- or 64-bit rows) and mask word w
+// at mask[w * maskStride + p].
+template <typename Metric>
+void addUnicastRoutes(DecisionRouteDb& db, const FlatTopology& f, const std::string& me,
+                      const PrefixHostTable& pt, const uint32_t* meta, const Metric* metric,
+                      const uint32_t* mask, size_t maskStride, int W, bool v4OverV6Nexthop) {
+  const uint32_t rb = f.rowPtr[f.id.at(me)];
+  for (uint32_t p = 0; p < uint32_t(pt.prefixes.size()); ++p) {
+    auto e = materializeRouteAt(f, rb, me, pt, p, meta[p], metric[p], &mask[p], maskStride, W,
+                                v4OverV6Nexthop, nullptr, OGS_POLICY_NONE, OGS_POLICY_NONE);
+    if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
+  }
+}
+// the enableV4 / best-route-selection bits of a launch's OGS_F_* word
+inline uint32_t routeFlags(bool enableV4, bool bestRouteSelection) {
+  return (enableV4 ? OGS_F_ENABLE_V4 : 0u) | (bestRouteSelection ? OGS_F_BEST_ROUTE_SELECTION : 0u);
+}
 // One DecisionRouteUpdate per variant (calculateUpdate, SpfSolver.cpp:21-56:
 // records without VALID are deletions, the rest materialised routes), built
 // on `threads` host threads (0: up to 16 / the hardware's).
@@ -1212,8 +1270,9 @@ DecisionRouteDb materializeRouteDb(
 // edges and no drain, else ogs_spf_routes_scenarios, or ogs_spf_routes_whatif
 // when a scenario moves a metric or soft-drains a node; route diff fused in;
 // form()); only the
-// changed records are gathered on the device (ogs_route_changes_gather) and
-// materialised. Areas past the LDS forms' node limit run every scenario kind
+// changed records are gathered on the device (CompactChanges:
+// ogs_route_changes_gather) and materialised; the what-if entries read the
+// scenario lists from one device copy (WhatifDeviceLists). Areas past the LDS forms' node limit run every scenario kind
 // through ogs_spf_routes_whatif_global (kGlobalState: one workgroup per
 // scenario on the global-state SPF, in chunks of scenarios), with the same
 // device diff and gather. Areas with zero / negative link metrics or path sums past 32
@@ -1347,6 +1406,23 @@ class LinkFailureSweep {
     uint32_t maxMetricList{0};
     void append(const Expanded& x);
   };
+  // The device copy of a Lists behind ogs_whatif_mods (ogs_scenario_mods
+  // reads its dead lists). uploadDead: the dead lists alone; upload: every
+  // list, a metric value with OGS_WHATIF_EDGE_UP where metricUp is set (all
+  // within 31 bits: the domain guards sent anything else to copies). Each
+  // uploads once. mods(first): the descriptor for scenarios [first, ..): the
+  // flag / metric pointers are NULL when that list is empty, and the offsets
+  // are absolute, so only the three offset arrays advance.
+  struct WhatifDeviceLists {
+    void uploadDead(const Lists& l);
+    void upload(const Lists& l);
+    ogs_whatif_mods mods(size_t firstScenario = 0) const;
+    DeviceBuffer deadOff, deadList, flagOff, flagNode, flagBits, metricOff, metricEdge, metricVal;
+
+   private:
+    bool dead_{false}, all_{false}, nodes_{false}, metrics_{false};
+    uint32_t maxMetricList_{0};
+  };
   // What the area and the lists' weights alone decide about the form (host
   // only): exact -> kTopologyCopies (exactOrder: in the extraction order),
   // needsGlobal -> kGlobalState; W = the source's next-hop words.
@@ -1416,7 +1492,7 @@ class LinkFailureSweep {
   // every variant's update, materialised on `threads` host threads (0: up to
   // 16 / the hardware's); variants are independent, so the batch splits
   std::vector<DecisionRouteUpdate> routeUpdates(int threads = 0) const;
-  ChangeRecords changeRecords() const;  // the fetched compact records
+  ChangeRecords changeRecords() const { return compact_.view(); }  // the fetched compact records
   DecisionRouteDb routeDb(size_t v) const;                // after fetchRecords
   std::vector<std::string> changedPrefixes(size_t v) const;  // after either
   std::pair<uint32_t, uint32_t> counts(size_t v) const;   // {update, delete}
@@ -1427,10 +1503,10 @@ class LinkFailureSweep {
   std::vector<int32_t> changedLabels(size_t v) const;
   uint64_t totalChangedNodes() const { return nodeOffsets_.empty() ? 0 : nodeOffsets_.back(); }
   bool nodeSegmentLabels() const { return labels_; }
-  uint64_t totalChanges() const { return offsets_.empty() ? 0 : offsets_.back(); }
+  uint64_t totalChanges() const { return compact_.offsets.empty() ? 0 : compact_.offsets.back(); }
   int nhWords() const { return W_; }
   const HostBatch& batch() const { return hb_; }
-  uint32_t flags() const;
+  uint32_t flags() const { return routeFlags(enableV4_, brs_); }
 
  private:
   static constexpr uint32_t kRegisterMax = 8;  // ogs_unit_mods.dead_per_unit limit
@@ -1476,12 +1552,10 @@ class LinkFailureSweep {
   DeviceBuffer bDesc_;
   Mode mode_{kRepair};
   Lists lists_;
-  DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_, dFlagOff_, dFlagNode_, dFlagBits_;
+  WhatifDeviceLists dLists_;
   bool forceBitset_{false};
   bool forceGlobal_{false}, needsGlobal_{false};
   size_t globalChunk_{0};
-  void uploadWhatifLists();  // the metric and flag lists (once)
-  bool whatifUploaded_{false};
   size_t globalChunkUnits(bool ownRows) const;
   void globalLaunch(const ogs_graph& g, const ogs_prefix_table& pt, const ogs_route_diff& diff,
                     uint32_t fl, const ogs_spf_out& out, void* stream);
@@ -1489,14 +1563,13 @@ class LinkFailureSweep {
   int deadPer_{0};  // dDead_'s dead_per_unit (0: not built yet)
   HostBatchImage img_;  // device copy of hb_
   DeviceBuffer dUnits_, dBaseUnit_, dDead_, dAdvClass_;
-  DeviceBuffer dDeadOff_, dDeadList_, dDrainOff_, dDrainList_;
+  DeviceBuffer dDrainOff_, dDrainList_;
   DeviceBuffer bDist_, bNh_, bMeta_, bMetric_, bMask_, bSel_;
   DeviceBuffer dDist_, dNh_, dMeta_, dMetric_, dMask_, dSel_, dChanged_, dCounts_;
-  DeviceBuffer dOffsets_, cPrefix_, cMeta_, cMetric_, cMask_;
+  CompactChanges compact_;  // fetchUpdates (copies form: the offsets alone)
   mutable std::optional<DecisionRouteDb> base_;
   std::vector<uint32_t> baseMeta_, baseMetric_, baseMask_;
-  std::vector<uint32_t> counts_, changed_, offsets_;
-  std::vector<uint32_t> cPrefixH_, cMetaH_, cMetricH_, cMaskH_;  // compact
+  std::vector<uint32_t> counts_, changed_;
   std::vector<uint32_t> meta_, metric_, mask_;                   // full
   // zero / negative metrics or 64-bit path sums: one topology per variant
   // through ogs_spf_routes (exactLaunch), updates by calculateUpdate
@@ -1518,7 +1591,9 @@ class LinkFailureSweep {
 // (SpfSolver.cpp:21-56) per node per scenario. Here every (source, scenario)
 // pair of one area is a unit of ogs_spf_routes_whatif_pairs: one base launch
 // (ogs_spf_routes over the batched sources), the scenario lists uploaded
-// once, then pair launches over chunks of units.
+// once (LinkFailureSweep::WhatifDeviceLists), then pair launches over chunks
+// of units, each chunk's changed records appended to one CompactChanges
+// (DESIGN.md 3.4l).
 //
 // The host-only plan: who is batched, the units, the chunks.
 struct NetworkWhatifPlan {
@@ -1557,9 +1632,10 @@ class NetworkWhatifSweep {
                      const std::vector<LinkFailureSweep::Scenario>& scenarios, bool enableV4,
                      bool enableBestRouteSelection = false, bool v4OverV6Nexthop = false);
   // Base launch when needed, then every chunk: pair launch and, with records,
-  // counts D2H -> host scan -> ogs_route_changes_gather -> the chunk's compact
-  // records D2H (the dense arrays are reused by the next chunk, so a launch
-  // with records returns with the batch's records on the host). records =
+  // counts D2H -> CompactChanges::gather (host scan, ogs_route_changes_gather,
+  // the chunk's compact records D2H; the dense arrays are reused by the next
+  // chunk, so a launch with records returns with the batch's records on the
+  // host). records =
   // false: bitmap and counts only (impact). Fallback sources launch their own
   // sweeps. If the pairs entry reports the call unsupported (its LDS budget),
   // every batched source becomes a fallback source.
@@ -1598,7 +1674,6 @@ class NetworkWhatifSweep {
   void replan();
   void runBase(void* stream);
   bool launchChunks(void* stream, bool records);  // false: the entry refused the call
-  ChangeRecords changeRecords() const;
   const LinkState& ls_;
   const PrefixState& ps_;
   std::vector<std::string> sources_;
@@ -1620,13 +1695,11 @@ class NetworkWhatifSweep {
   bool impactFetched_{false}, updatesFetched_{false};
   void upload();
   DeviceBuffer dUnits_, dBase_, dScen_, dBaseUnits_, dAdvClass_;
-  DeviceBuffer dDeadOff_, dDeadList_, dFlagOff_, dFlagNode_, dFlagBits_;
-  DeviceBuffer dMetricOff_, dMetricEdge_, dMetricVal_;
+  LinkFailureSweep::WhatifDeviceLists dLists_;
   DeviceBuffer bDist_, bNh_, bMeta_, bMetric_, bMask_, bSel_;
   DeviceBuffer dMeta_, dMetric_, dMask_, dChanged_, dCounts_;
-  DeviceBuffer dOffsets_, cPrefix_, cMeta_, cMetric_, cMask_;
-  std::vector<uint32_t> counts_, offsets_;
-  std::vector<uint32_t> cPrefixH_, cMetaH_, cMetricH_, cMaskH_;
+  std::vector<uint32_t> counts_;
+  CompactChanges compact_;
   mutable std::map<size_t, DecisionRouteDb> base_;
 };
 

@@ -151,7 +151,7 @@ void NetworkWhatifSweep::setChunkBytes(size_t bytes) {
   plan_.impactChunks = chunkBounds(plan_.pairs.size(), plan_.impactUnitBytes, chunkBytes_);
   launched_ = impactFetched_ = updatesFetched_ = false;
   counts_.clear();
-  offsets_.clear();
+  compact_.reset(0, 1);
 }
 
 // graph, table, units, pair indices and the scenario lists: once
@@ -174,23 +174,7 @@ void NetworkWhatifSweep::upload() {
   dUnits_.upload(units.data(), units.size());
   dBase_.upload(base.data(), base.size());
   dScen_.upload(scen.data(), scen.size());
-  dDeadOff_.upload(lists_.deadOff.data(), lists_.deadOff.size());
-  dDeadList_.upload(lists_.deadList.data(), lists_.deadList.size());
-  if (!lists_.flagNode.empty()) {
-    dFlagOff_.upload(lists_.flagOff.data(), lists_.flagOff.size());
-    dFlagNode_.upload(lists_.flagNode.data(), lists_.flagNode.size());
-    dFlagBits_.upload(lists_.flagBits.data(), lists_.flagBits.size());
-  }
-  if (!lists_.metricEdge.empty()) {
-    // all within 31 bits (the domain guards sent anything else to the fallback)
-    std::vector<uint32_t> vals(lists_.metricVal.begin(), lists_.metricVal.end());
-    for (size_t i = 0; i < vals.size(); ++i) {
-      if (lists_.metricUp[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
-    }
-    dMetricOff_.upload(lists_.metricOff.data(), lists_.metricOff.size());
-    dMetricEdge_.upload(lists_.metricEdge.data(), lists_.metricEdge.size());
-    dMetricVal_.upload(vals.data(), vals.size());
-  }
+  dLists_.upload(lists_);
   const std::vector<uint32_t> cls = advClasses(table_);
   dAdvClass_.upload(cls.data(), cls.size());
   const size_t B = std::max<size_t>(plan_.batched.size(), 1);
@@ -206,9 +190,8 @@ void NetworkWhatifSweep::runBase(void* stream) {
   const ogs_prefix_table pt = img_.table(hb_);
   ogs_spf_out out{bDist_.get(),   bNh_.as<uint32_t>(),   bMeta_.as<uint32_t>(),
                   bMetric_.get(), bMask_.as<uint32_t>(), bSel_.as<uint32_t>()};
-  const uint32_t fl = (enableV4_ ? OGS_F_ENABLE_V4 : 0u) | (brs_ ? OGS_F_BEST_ROUTE_SELECTION : 0u);
-  ogsCheck(ogs_spf_routes(&g, &pt, dBaseUnits_.as<ogs_unit>(), int32_t(plan_.batched.size()), fl,
-                          1, &out, stream),
+  ogsCheck(ogs_spf_routes(&g, &pt, dBaseUnits_.as<ogs_unit>(), int32_t(plan_.batched.size()),
+                          routeFlags(enableV4_, brs_), 1, &out, stream),
            "ogs_spf_routes(bases)");
   baseRun_ = true;
   base_.clear();
@@ -225,35 +208,18 @@ bool NetworkWhatifSweep::launchChunks(void* stream, bool records) {
   }
   const ogs_graph g = img_.graph(hb_, 1);
   const ogs_prefix_table pt = img_.table(hb_);
-  const bool nodes = !lists_.flagNode.empty(), metrics = !lists_.metricEdge.empty();
-  // absolute offsets into the lists: every chunk passes the same mods
-  const ogs_whatif_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
-                             nodes ? dFlagOff_.as<uint32_t>() : nullptr,
-                             nodes ? dFlagNode_.as<uint32_t>() : nullptr,
-                             nodes ? dFlagBits_.as<uint8_t>() : nullptr,
-                             metrics ? dMetricOff_.as<uint32_t>() : nullptr,
-                             metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
-                             metrics ? dMetricVal_.as<uint32_t>() : nullptr,
-                             lists_.maxMetricList};
-  uint32_t fl = (enableV4_ ? OGS_F_ENABLE_V4 : 0u) | (brs_ ? OGS_F_BEST_ROUTE_SELECTION : 0u) |
-      OGS_F_INCREMENTAL | OGS_F_CHANGED_ONLY;
+  // the pairs index the scenarios themselves: every chunk passes the same mods
+  const ogs_whatif_mods mods = dLists_.mods();
+  uint32_t fl = routeFlags(enableV4_, brs_) | OGS_F_INCREMENTAL | OGS_F_CHANGED_ONLY;
   if (lists_.restores) fl |= OGS_F_RESTORE;
   ogs_spf_out out{};
   if (records) {
     out.meta = dMeta_.as<uint32_t>();
     out.metric = dMetric_.get();
     out.mask = dMask_.as<uint32_t>();
-  }
-  if (records) {
     counts_.assign(U * 2, 0);
-    offsets_.assign(U + 1, 0);
-    cPrefixH_.clear();
-    cMetaH_.clear();
-    cMetricH_.clear();
-    cMaskH_.clear();
+    compact_.reset(U, 1);
   }
-  uint64_t total = 0;
-  std::vector<uint32_t> local;
   for (size_t c = 0; c + 1 < chunks.size(); ++c) {
     const size_t c0 = chunks[c], n = chunks[c + 1] - c0;
     const ogs_whatif_pairs pairs{dBase_.as<uint32_t>() + c0, dScen_.as<uint32_t>() + c0,
@@ -271,35 +237,9 @@ bool NetworkWhatifSweep::launchChunks(void* stream, bool records) {
     ogsCheck(ogs_memcpy_d2h(&counts_[c0 * 2], dCounts_.as<uint32_t>() + c0 * 2, n * 8, stream),
              "ogs_memcpy_d2h");
     ogsCheck(ogs_stream_sync(stream), "ogs_stream_sync");
-    local.assign(n + 1, 0);
-    uint64_t t = 0;
-    for (size_t i = 0; i < n; ++i) {
-      local[i] = uint32_t(t);
-      const uint32_t up = counts_[(c0 + i) * 2], del = counts_[(c0 + i) * 2 + 1];
-      if (up != OGS_WHATIF_REFUSED) t += uint64_t(up) + del;
-      if (total + t > 0xFFFFFFFFull) throw std::length_error("NetworkWhatifSweep: > 2^32 changes");
-      offsets_[c0 + i + 1] = uint32_t(total + t);
-    }
-    local[n] = uint32_t(t);
-    if (t == 0) continue;
-    dOffsets_.upload(local.data(), local.size(), stream);
-    for (auto* b : {&cPrefix_, &cMeta_, &cMetric_, &cMask_}) b->resize(t * 4);
-    const ogs_spf_out rec{nullptr, nullptr, dMeta_.as<uint32_t>(), dMetric_.get(),
-                          dMask_.as<uint32_t>(), nullptr};
-    const ogs_route_changes ch{dOffsets_.as<uint32_t>(), size_t(t), cPrefix_.as<uint32_t>(),
-                               cMeta_.as<uint32_t>(), cMetric_.as<uint32_t>(),
-                               cMask_.as<uint32_t>()};
-    ogsCheck(ogs_route_changes_gather(dChanged_.as<uint32_t>(), int32_t(n), int32_t(Sp_), &rec, 1,
-                                      &ch, stream),
-             "ogs_route_changes_gather");
-    for (auto* h : {&cPrefixH_, &cMetaH_, &cMetricH_, &cMaskH_}) h->resize(total + t);
-    cPrefix_.download(&cPrefixH_[total], t, stream);
-    cMeta_.download(&cMetaH_[total], t, stream);
-    cMetric_.download(&cMetricH_[total], t, stream);
-    cMask_.download(&cMaskH_[total], t, stream);
+    compact_.gather(c0, n, &counts_[c0 * 2], dChanged_.as<uint32_t>(), out, Sp_, stream);
     // the host vectors grow and the offsets are rewritten by the next chunk
     ogsCheck(ogs_stream_sync(stream), "ogs_stream_sync");
-    total += t;
   }
   return true;
 }
@@ -380,19 +320,6 @@ std::vector<uint32_t> NetworkWhatifSweep::affectedSources(size_t k) const {
   return out;
 }
 
-ChangeRecords NetworkWhatifSweep::changeRecords() const {
-  ChangeRecords c;
-  c.offsets = offsets_.data();
-  c.variants = plan_.pairs.size();
-  c.prefix = cPrefixH_.data();
-  c.meta = cMetaH_.data();
-  c.metric = cMetricH_.data();
-  c.mask = cMaskH_.data();
-  c.total = cPrefixH_.size();
-  c.W = 1;
-  return c;
-}
-
 std::vector<std::string> NetworkWhatifSweep::changedPrefixes(size_t s, size_t k) const {
   check(s, k);
   if (!updatesFetched_) throw std::logic_error("NetworkWhatifSweep: fetchUpdates() first");
@@ -403,8 +330,8 @@ std::vector<std::string> NetworkWhatifSweep::changedPrefixes(size_t s, size_t k)
   }
   const size_t u = unit_[size_t(row_[s]) * K_ + k];
   std::vector<std::string> out;
-  for (uint32_t i = offsets_[u]; i < offsets_[u + 1]; ++i) {
-    out.push_back(table_.prefixes.at(cPrefixH_[i]));
+  for (uint32_t i = compact_.offsets[u]; i < compact_.offsets[u + 1]; ++i) {
+    out.push_back(table_.prefixes.at(compact_.prefix[i]));
   }
   std::sort(out.begin(), out.end());
   return out;
@@ -425,7 +352,7 @@ DecisionRouteUpdate NetworkWhatifSweep::routeUpdate(size_t s, size_t k) const {
   if (counts_[2 * u] == OGS_WHATIF_REFUSED) {
     throw std::logic_error("NetworkWhatifSweep: the device refused the pair");
   }
-  return materializeUpdate(ls_.flat(), sources_[s], table_, changeRecords(), u, v4OverV6_);
+  return materializeUpdate(ls_.flat(), sources_[s], table_, compact_.view(), u, v4OverV6_);
 }
 
 // the source's base RouteDb from its row of the base launch's records
@@ -443,12 +370,8 @@ const DecisionRouteDb& NetworkWhatifSweep::baseRouteDb(size_t s) const {
   ogsCheck(ogs_memcpy_d2h(mask.data(), bMask_.as<uint32_t>() + r * Sp_, Sp_ * 4, nullptr), "d2h");
   ogsCheck(ogs_stream_sync(nullptr), "ogs_stream_sync");
   DecisionRouteDb db;
-  const FlatTopology& f = ls_.flat();
-  for (uint32_t p = 0; p < uint32_t(table_.prefixes.size()); ++p) {
-    auto e = materializeRoute(f, sources_[s], table_, p, meta[p], metric[p], &mask[p], Sp_, 1,
-                              v4OverV6_, nullptr, OGS_POLICY_NONE, OGS_POLICY_NONE);
-    if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
-  }
+  addUnicastRoutes(db, ls_.flat(), sources_[s], table_, meta.data(), metric.data(), mask.data(),
+                   Sp_, 1, v4OverV6_);
   return base_.emplace(s, std::move(db)).first->second;
 }
 

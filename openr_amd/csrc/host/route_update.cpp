@@ -369,7 +369,7 @@ void LinkFailureSweep::uploadRegisterSlots() {
 void LinkFailureSweep::reselect() {
   form_ = selectForm();
   recordsRun_ = changedOnlyRun_ = false;
-  offsets_.clear();
+  compact_.offsets.clear();
   changed_.clear();
   counts_.clear();
   meta_.clear();
@@ -389,7 +389,7 @@ void LinkFailureSweep::setListForm(bool forceBitset) {
 void LinkFailureSweep::setGlobalForm(bool forceGlobal) {
   forceGlobal_ = forceGlobal;
   reselect();
-  if (form_ == kGlobalState) uploadWhatifLists();
+  if (form_ == kGlobalState && !exact_) dLists_.upload(lists_);
 }
 
 void LinkFailureSweep::setGlobalChunk(size_t n) {
@@ -397,25 +397,46 @@ void LinkFailureSweep::setGlobalChunk(size_t n) {
   reselect();
 }
 
-// The metric and flag lists of ogs_whatif_mods (the dead lists are always
-// there): for the what-if entry when a scenario moves a metric or sets a
-// soft-drain bit, for the global form whenever it is selected.
-void LinkFailureSweep::uploadWhatifLists() {
-  if (whatifUploaded_ || exact_) return;
-  whatifUploaded_ = true;
-  // all within 31 bits (the domain guards sent anything else to copies)
-  std::vector<uint32_t> vals(lists_.metricVal.begin(), lists_.metricVal.end());
-  for (size_t i = 0; i < vals.size(); ++i) {
-    if (lists_.metricUp[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
+void LinkFailureSweep::WhatifDeviceLists::uploadDead(const Lists& l) {
+  if (dead_) return;
+  dead_ = true;
+  deadOff.upload(l.deadOff.data(), l.deadOff.size());
+  deadList.upload(l.deadList.data(), l.deadList.size());
+}
+
+void LinkFailureSweep::WhatifDeviceLists::upload(const Lists& l) {
+  uploadDead(l);
+  if (all_) return;
+  all_ = true;
+  nodes_ = !l.flagNode.empty();
+  metrics_ = !l.metricEdge.empty();
+  maxMetricList_ = l.maxMetricList;
+  if (nodes_) {
+    flagOff.upload(l.flagOff.data(), l.flagOff.size());
+    flagNode.upload(l.flagNode.data(), l.flagNode.size());
+    flagBits.upload(l.flagBits.data(), l.flagBits.size());
   }
-  dMetricOff_.upload(lists_.metricOff.data(), lists_.metricOff.size());
-  dMetricEdge_.upload(lists_.metricEdge.data(), lists_.metricEdge.size());
-  dMetricVal_.upload(vals.data(), vals.size());
-  if (!lists_.flagNode.empty()) {
-    dFlagOff_.upload(lists_.flagOff.data(), lists_.flagOff.size());
-    dFlagNode_.upload(lists_.flagNode.data(), lists_.flagNode.size());
-    dFlagBits_.upload(lists_.flagBits.data(), lists_.flagBits.size());
+  if (metrics_) {
+    std::vector<uint32_t> vals(l.metricVal.begin(), l.metricVal.end());
+    for (size_t i = 0; i < vals.size(); ++i) {
+      if (l.metricUp[i]) vals[i] |= OGS_WHATIF_EDGE_UP;
+    }
+    metricOff.upload(l.metricOff.data(), l.metricOff.size());
+    metricEdge.upload(l.metricEdge.data(), l.metricEdge.size());
+    metricVal.upload(vals.data(), vals.size());
   }
+}
+
+ogs_whatif_mods LinkFailureSweep::WhatifDeviceLists::mods(size_t firstScenario) const {
+  return ogs_whatif_mods{deadOff.as<uint32_t>() + firstScenario,
+                         deadList.as<uint32_t>(),
+                         nodes_ ? flagOff.as<uint32_t>() + firstScenario : nullptr,
+                         nodes_ ? flagNode.as<uint32_t>() : nullptr,
+                         nodes_ ? flagBits.as<uint8_t>() : nullptr,
+                         metrics_ ? metricOff.as<uint32_t>() + firstScenario : nullptr,
+                         metrics_ ? metricEdge.as<uint32_t>() : nullptr,
+                         metrics_ ? metricVal.as<uint32_t>() : nullptr,
+                         maxMetricList_};
 }
 
 // Scenarios per ogs_spf_routes_whatif_global call: the most whose workspace
@@ -439,19 +460,12 @@ size_t LinkFailureSweep::globalChunkUnits(bool ownRows) const {
 void LinkFailureSweep::globalLaunch(const ogs_graph& g, const ogs_prefix_table& pt,
                                     const ogs_route_diff& diff, uint32_t fl,
                                     const ogs_spf_out& out, void* stream) {
-  uploadWhatifLists();
+  dLists_.upload(lists_);
   const size_t U = numVariants(), Sn = size_t(std::max(hb_.maxNodes, 1));
   const size_t chunk = globalChunkUnits(out.dist && out.nh);
-  const bool nodes = !lists_.flagNode.empty(), metrics = !lists_.metricEdge.empty();
   for (size_t c0 = 0; c0 < U; c0 += chunk) {
     const size_t n = std::min(chunk, U - c0);
-    ogs_whatif_mods mods{dDeadOff_.as<uint32_t>() + c0, dDeadList_.as<uint32_t>(),
-                         nodes ? dFlagOff_.as<uint32_t>() + c0 : nullptr,
-                         nodes ? dFlagNode_.as<uint32_t>() : nullptr,
-                         nodes ? dFlagBits_.as<uint8_t>() : nullptr,
-                         metrics ? dMetricOff_.as<uint32_t>() + c0 : nullptr,
-                         metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
-                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, lists_.maxMetricList};
+    const ogs_whatif_mods mods = dLists_.mods(c0);
     ogs_route_diff d = diff;
     d.changed += c0 * words_;
     d.counts += c0 * 2;
@@ -517,13 +531,12 @@ LinkFailureSweep::LinkFailureSweep(
   dUnits_.upload(units.data(), units.size());
   dBaseUnit_.upload(&base, 1);
   if (form_ == kRegisterList) uploadRegisterSlots();
-  dDeadOff_.upload(lists_.deadOff.data(), lists_.deadOff.size());
-  dDeadList_.upload(lists_.deadList.data(), lists_.deadList.size());
+  dLists_.uploadDead(lists_);
   if (!lists_.drainList.empty()) {
     dDrainOff_.upload(lists_.drainOff.data(), lists_.drainOff.size());
     dDrainList_.upload(lists_.drainList.data(), lists_.drainList.size());
   }
-  if ((lists_.whatif || form_ == kGlobalState) && !exact_) uploadWhatifLists();
+  if ((lists_.whatif || form_ == kGlobalState) && !exact_) dLists_.upload(lists_);
   {
     const std::vector<uint32_t> cls = advClasses(table_);
     dAdvClass_.upload(cls.data(), cls.size());
@@ -592,18 +605,24 @@ void LinkFailureSweep::exactLaunch(void* stream) {
       for (uint32_t i = lists_.deadOff[t - 1]; i < lists_.deadOff[t]; ++i) {
         hb.edges[e0 + lists_.deadList[i]] |= OGS_EDGE_DOWN;
       }
-      // a drain, as LinkState::patchFlat encodes it: the node's flag and
-      // OGS_EDGE_DST_OVERLOADED on every edge into it (the reverse of each
-      // edge of its row: links are two-way)
-      for (uint32_t i = lists_.drainOff[t - 1]; i < lists_.drainOff[t]; ++i) {
-        const uint32_t x = lists_.drainList[i];
-        hb.nodeFlags[n0 + x] |= OGS_NODE_OVERLOADED;
+      // OGS_EDGE_DST_OVERLOADED on (or off) every edge into node x: the
+      // reverse of each edge of its row (links are two-way)
+      auto markEdgesInto = [&](uint32_t x, bool overloaded) {
         for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
           const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
           for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
-            if (f.edgeLink[r] == f.edgeLink[e]) hb.edges[e0 + r] |= OGS_EDGE_DST_OVERLOADED;
+            if (f.edgeLink[r] != f.edgeLink[e]) continue;
+            uint64_t& w = hb.edges[e0 + r];
+            w = overloaded ? w | OGS_EDGE_DST_OVERLOADED : w & ~uint64_t(OGS_EDGE_DST_OVERLOADED);
           }
         }
+      };
+      // a drain, as LinkState::patchFlat encodes it: the node's flag and
+      // OGS_EDGE_DST_OVERLOADED on every edge into it
+      for (uint32_t i = lists_.drainOff[t - 1]; i < lists_.drainOff[t]; ++i) {
+        const uint32_t x = lists_.drainList[i];
+        hb.nodeFlags[n0 + x] |= OGS_NODE_OVERLOADED;
+        markEdgesInto(x, true);
       }
       // metric overrides, as LinkState::patchFlat re-encodes a moved metric,
       // and the soft-drain bits (link_state.cpp: the node's flags alone)
@@ -627,13 +646,7 @@ void LinkFailureSweep::exactLaunch(void* stream) {
         uint8_t& nf = hb.nodeFlags[n0 + x];
         const bool was = (nf & OGS_NODE_OVERLOADED) != 0;
         nf = uint8_t((nf & ~clr) | (lists_.flagBits[i] & 0x0Fu));
-        if (!was || (nf & OGS_NODE_OVERLOADED)) continue;
-        for (uint32_t e = f.rowPtr[x]; e < f.rowPtr[x + 1]; ++e) {
-          const uint32_t o = uint32_t(f.edges[e]) & OGS_EDGE_DST_MASK;
-          for (uint32_t r = f.rowPtr[o]; r < f.rowPtr[o + 1]; ++r) {
-            if (f.edgeLink[r] == f.edgeLink[e]) hb.edges[e0 + r] &= ~uint64_t(OGS_EDGE_DST_OVERLOADED);
-          }
-        }
+        if (was && !(nf & OGS_NODE_OVERLOADED)) markEdgesInto(x, false);
       }
     }
     std::vector<ogs_unit> us(n);
@@ -678,18 +691,11 @@ void LinkFailureSweep::exactLaunch(void* stream) {
 void LinkFailureSweep::exactFetch(void* /*stream*/) {
   if (!recordsRun_) throw std::logic_error("LinkFailureSweep: launch() first");
   const size_t U = numVariants();
-  const std::vector<uint32_t>& meta = xMeta_;
-  const std::vector<uint32_t>& mask = xMask_;
-  const std::vector<uint64_t>& metric = xMetric_;
   const FlatTopology& f = ls_.flat();
   auto dbOf = [&](size_t t) {
     DecisionRouteDb db;
-    for (uint32_t p = 0; p < uint32_t(table_.prefixes.size()); ++p) {
-      auto e = materializeRoute(f, me_, table_, p, meta[t * Sp_ + p], metric[t * Sp_ + p],
-                                &mask[t * W_ * Sp_ + p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE,
-                                OGS_POLICY_NONE);
-      if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
-    }
+    addUnicastRoutes(db, f, me_, table_, &xMeta_[t * Sp_], &xMetric_[t * Sp_],
+                     &xMask_[t * W_ * Sp_], Sp_, W_, v4OverV6_);
     if (labels_) {  // the copy's own rows through the solver's label pass
       const size_t Sn = size_t(std::max(hb_.maxNodes, 1)), rw = (Sn + 31) / 32;
       LabelRoutes labelToNode;
@@ -703,18 +709,13 @@ void LinkFailureSweep::exactFetch(void* /*stream*/) {
   xDb_.clear();
   xUpd_.clear();
   counts_.assign(2 * U, 0);
-  offsets_.assign(U + 1, 0);
   for (size_t v = 0; v < U; ++v) {
     xDb_.push_back(dbOf(v + 1));
     xUpd_.push_back(base_->calculateUpdate(xDb_.back()));
     counts_[2 * v] = uint32_t(xUpd_.back().unicastRoutesToUpdate.size());
     counts_[2 * v + 1] = uint32_t(xUpd_.back().unicastRoutesToDelete.size());
-    offsets_[v + 1] = offsets_[v] + counts_[2 * v] + counts_[2 * v + 1];
   }
-}
-
-uint32_t LinkFailureSweep::flags() const {
-  return (enableV4_ ? OGS_F_ENABLE_V4 : 0u) | (brs_ ? OGS_F_BEST_ROUTE_SELECTION : 0u);
+  scanChangeCounts<2>(counts_.data(), U, compact_.offsets);
 }
 
 void LinkFailureSweep::runBase(void* stream) {
@@ -733,7 +734,7 @@ void LinkFailureSweep::runBase(void* stream) {
 void LinkFailureSweep::launch(void* stream, bool records) {
   if (copies()) return exactLaunch(stream);  // records are always written
   if (!baseRun_) runBase(stream);
-  offsets_.clear();  // results of an earlier launch are stale now
+  compact_.offsets.clear();  // results of an earlier launch are stale now
   changed_.clear();
   meta_.clear();
   counts_.clear();
@@ -777,14 +778,7 @@ void LinkFailureSweep::launch(void* stream, bool records) {
                                      &mods, &diff, fl, W_, &out, stream),
              "ogs_spf_routes_variants");
   } else if (lists_.whatif) {
-    const bool nodes = !lists_.flagNode.empty(), metrics = !lists_.metricEdge.empty();
-    ogs_whatif_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
-                         nodes ? dFlagOff_.as<uint32_t>() : nullptr,
-                         nodes ? dFlagNode_.as<uint32_t>() : nullptr,
-                         nodes ? dFlagBits_.as<uint8_t>() : nullptr,
-                         metrics ? dMetricOff_.as<uint32_t>() : nullptr,
-                         metrics ? dMetricEdge_.as<uint32_t>() : nullptr,
-                         metrics ? dMetricVal_.as<uint32_t>() : nullptr, lists_.maxMetricList};
+    const ogs_whatif_mods mods = dLists_.mods();
     const int rc = ogs_spf_routes_whatif(&g, &pt, dUnits_.as<ogs_unit>(),
                                          int32_t(numVariants()), &mods, &diff, fl, W_, &out,
                                          stream);
@@ -797,7 +791,7 @@ void LinkFailureSweep::launch(void* stream, bool records) {
     ogsCheck(rc, "ogs_spf_routes_whatif");
   } else {
     const bool drains = !lists_.drainList.empty();
-    ogs_scenario_mods mods{dDeadOff_.as<uint32_t>(), dDeadList_.as<uint32_t>(),
+    ogs_scenario_mods mods{dLists_.deadOff.as<uint32_t>(), dLists_.deadList.as<uint32_t>(),
                            drains ? dDrainOff_.as<uint32_t>() : nullptr,
                            drains ? dDrainList_.as<uint32_t>() : nullptr};
     const int rc = ogs_spf_routes_scenarios(&g, &pt, dUnits_.as<ogs_unit>(),
@@ -830,6 +824,51 @@ void LinkFailureSweep::runNodeDiff(const ogs_graph& g, void* stream) {
            "ogs_spf_node_diff");
 }
 
+void CompactChanges::reset(size_t units, int W) {
+  W_ = W;
+  done_ = 0;
+  offsets.assign(units + 1, 0);
+  for (auto* h : {&prefix, &meta, &metric, &mask}) h->clear();
+}
+
+void CompactChanges::gather(size_t u0, size_t n, const uint32_t* counts, const uint32_t* dChanged,
+                            const ogs_spf_out& rec, size_t Sp, void* stream) {
+  if (u0 != done_ || u0 + n + 1 > offsets.size() || (W_ > 1 && done_ != 0)) {
+    throw std::logic_error("CompactChanges: chunks append in unit order, and only at W = 1");
+  }
+  done_ += n;
+  const size_t held = prefix.size();
+  const size_t t = scanChangeCounts<2>(counts, n, local_, held);
+  for (size_t i = 1; i <= n; ++i) offsets[u0 + i] = uint32_t(held + local_[i]);
+  if (t == 0) return;
+  dOffsets.upload(local_.data(), local_.size(), stream);
+  for (auto* b : {&cPrefix, &cMeta, &cMetric}) b->resize(t * 4);
+  cMask.resize(t * W_ * 4);
+  const ogs_route_changes ch{dOffsets.as<uint32_t>(), t, cPrefix.as<uint32_t>(),
+                             cMeta.as<uint32_t>(), cMetric.as<uint32_t>(), cMask.as<uint32_t>()};
+  ogsCheck(ogs_route_changes_gather(dChanged, int32_t(n), int32_t(Sp), &rec, W_, &ch, stream),
+           "ogs_route_changes_gather");
+  for (auto* h : {&prefix, &meta, &metric}) h->resize(held + t);
+  mask.resize((held + t) * W_);
+  cPrefix.download(&prefix[held], t, stream);
+  cMeta.download(&meta[held], t, stream);
+  cMetric.download(&metric[held], t, stream);
+  cMask.download(&mask[held * W_], t * W_, stream);
+}
+
+ChangeRecords CompactChanges::view() const {
+  ChangeRecords c;
+  c.offsets = offsets.data();
+  c.variants = offsets.empty() ? 0 : offsets.size() - 1;
+  c.prefix = prefix.data();
+  c.meta = meta.data();
+  c.metric = metric.data();
+  c.mask = mask.data();
+  c.total = prefix.size();
+  c.W = W_;
+  return c;
+}
+
 void LinkFailureSweep::fetchUpdates(void* stream) {
   if (copies()) return exactFetch(stream);
   if (!recordsRun_) {
@@ -843,48 +882,14 @@ void LinkFailureSweep::fetchUpdates(void* stream) {
     if (U) dNodeCounts_.download(nodeCounts_.data(), U, stream);
   }
   ogsCheck(ogs_stream_sync(stream), "ogs_stream_sync");
-  offsets_.assign(U + 1, 0);
-  uint64_t total = 0;
-  for (size_t v = 0; v < U; ++v) {
-    offsets_[v] = uint32_t(total);
-    total += uint64_t(counts_[2 * v]) + counts_[2 * v + 1];
-    if (total > 0xFFFFFFFFull) throw std::length_error("LinkFailureSweep: > 2^32 changes");
-  }
-  offsets_[U] = uint32_t(total);
-  const size_t T = std::max<size_t>(total, 1);
-  dOffsets_.upload(offsets_.data(), offsets_.size(), stream);
-  cPrefix_.resize(T * 4);
-  cMeta_.resize(T * 4);
-  cMetric_.resize(T * 4);
-  cMask_.resize(T * W_ * 4);
-  ogs_spf_out rec{nullptr, nullptr, dMeta_.as<uint32_t>(), dMetric_.get(),
-                  dMask_.as<uint32_t>(), nullptr};
-  ogs_route_changes ch{dOffsets_.as<uint32_t>(), size_t(total), cPrefix_.as<uint32_t>(),
-                       cMeta_.as<uint32_t>(), cMetric_.as<uint32_t>(),
-                       cMask_.as<uint32_t>()};
-  ogsCheck(ogs_route_changes_gather(dChanged_.as<uint32_t>(), int32_t(U), int32_t(Sp_), &rec,
-                                    W_, &ch, stream),
-           "ogs_route_changes_gather");
-  cPrefixH_.resize(total);
-  cMetaH_.resize(total);
-  cMetricH_.resize(total);
-  cMaskH_.resize(total * W_);
-  if (total) {
-    cPrefix_.download(cPrefixH_.data(), total, stream);
-    cMeta_.download(cMetaH_.data(), total, stream);
-    cMetric_.download(cMetricH_.data(), total, stream);
-    cMask_.download(cMaskH_.data(), total * W_, stream);
-  }
+  // one chunk of all the units; the sync below ends it
+  compact_.reset(U, W_);
+  const ogs_spf_out rec{nullptr, nullptr, dMeta_.as<uint32_t>(), dMetric_.get(),
+                        dMask_.as<uint32_t>(), nullptr};
+  compact_.gather(0, U, counts_.data(), dChanged_.as<uint32_t>(), rec, Sp_, stream);
   if (labels_) {  // the same for the changed SPF rows
     const size_t Sn = size_t(std::max(hb_.maxNodes, 1));
-    nodeOffsets_.assign(U + 1, 0);
-    uint64_t nodes = 0;
-    for (size_t v = 0; v < U; ++v) {
-      nodeOffsets_[v] = uint32_t(nodes);
-      nodes += nodeCounts_[v];
-      if (nodes > 0xFFFFFFFFull) throw std::length_error("LinkFailureSweep: > 2^32 changes");
-    }
-    nodeOffsets_[U] = uint32_t(nodes);
+    const uint64_t nodes = scanChangeCounts<1>(nodeCounts_.data(), U, nodeOffsets_);
     const size_t Tn = std::max<size_t>(nodes, 1);
     dNodeOffsets_.upload(nodeOffsets_.data(), nodeOffsets_.size(), stream);
     cNode_.resize(Tn * 4);
@@ -970,12 +975,8 @@ const DecisionRouteDb& LinkFailureSweep::baseRouteDb() const {
   if (baseMeta_.empty()) throw std::logic_error("LinkFailureSweep: nothing fetched yet");
   if (!base_) {
     DecisionRouteDb db;
-    const FlatTopology& f = ls_.flat();
-    for (uint32_t p = 0; p < uint32_t(table_.prefixes.size()); ++p) {
-      auto e = materializeRoute(f, me_, table_, p, baseMeta_[p], baseMetric_[p],
-                                &baseMask_[p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE, OGS_POLICY_NONE);
-      if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
-    }
+    addUnicastRoutes(db, ls_.flat(), me_, table_, baseMeta_.data(), baseMetric_.data(),
+                     baseMask_.data(), Sp_, W_, v4OverV6_);
     if (labels_) addBaseLabelRoutes(db);
     base_ = std::move(db);
   }
@@ -1149,24 +1150,14 @@ std::vector<DecisionRouteUpdate> materializeUpdates(const FlatTopology& f, const
   return out;
 }
 
-ChangeRecords LinkFailureSweep::changeRecords() const {
-  ChangeRecords c;
-  c.offsets = offsets_.data();
-  c.variants = numVariants();
-  c.prefix = cPrefixH_.data();
-  c.meta = cMetaH_.data();
-  c.metric = cMetricH_.data();
-  c.mask = cMaskH_.data();
-  c.total = cPrefixH_.size();
-  c.W = W_;
-  return c;
-}
-
 DecisionRouteUpdate LinkFailureSweep::routeUpdate(size_t v) const {
-  if (v >= numVariants() || offsets_.size() != numVariants() + 1) {
+  if (v >= numVariants() || compact_.offsets.size() != numVariants() + 1) {
     throw std::out_of_range("LinkFailureSweep::routeUpdate: variant / fetchUpdates");
   }
   if (copies()) return xUpd_.at(v);
+  if (counts_[2 * v] == OGS_WHATIF_REFUSED) {
+    throw std::logic_error("LinkFailureSweep: the device refused the scenario");
+  }
   const FlatTopology& f = ls_.flat();
   DecisionRouteUpdate u =
       updateOf(f, f.rowPtr[f.id.at(me_)], me_, table_, changeRecords(), v, v4OverV6_);
@@ -1176,7 +1167,7 @@ DecisionRouteUpdate LinkFailureSweep::routeUpdate(size_t v) const {
 
 std::vector<DecisionRouteUpdate> LinkFailureSweep::routeUpdates(int threads) const {
   const size_t V = numVariants();
-  if (offsets_.size() != V + 1) {
+  if (compact_.offsets.size() != V + 1) {
     throw std::out_of_range("LinkFailureSweep::routeUpdates: fetchUpdates first");
   }
   if (copies()) return xUpd_;
@@ -1196,13 +1187,8 @@ DecisionRouteDb LinkFailureSweep::routeDb(size_t v) const {
     throw std::out_of_range("LinkFailureSweep::routeDb: variant / fetchRecords");
   }
   DecisionRouteDb db;
-  const FlatTopology& f = ls_.flat();
-  for (uint32_t p = 0; p < uint32_t(table_.prefixes.size()); ++p) {
-    auto e = materializeRoute(f, me_, table_, p, meta_[v * Sp_ + p], metric_[v * Sp_ + p],
-                              &mask_[v * W_ * Sp_ + p], Sp_, W_, v4OverV6_, nullptr, OGS_POLICY_NONE,
-                              OGS_POLICY_NONE);
-    if (e) db.unicastRoutes.emplace(e->prefix, std::move(*e));
-  }
+  addUnicastRoutes(db, ls_.flat(), me_, table_, &meta_[v * Sp_], &metric_[v * Sp_],
+                   &mask_[v * W_ * Sp_], Sp_, W_, v4OverV6_);
   if (labels_) {
     const size_t Sn = baseDist_.size();
     if (counts_[2 * v] == OGS_WHATIF_REFUSED) {  // wrote no rows: no MPLS change
@@ -1222,9 +1208,9 @@ std::vector<std::string> LinkFailureSweep::changedPrefixes(size_t v) const {
     for (const auto& [p, _] : xUpd_[v].unicastRoutesToUpdate) out.push_back(p);
     out.insert(out.end(), xUpd_[v].unicastRoutesToDelete.begin(),
                xUpd_[v].unicastRoutesToDelete.end());
-  } else if (offsets_.size() == numVariants() + 1) {
-    for (uint32_t i = offsets_[v]; i < offsets_[v + 1]; ++i) {
-      out.push_back(table_.prefixes.at(cPrefixH_[i]));
+  } else if (compact_.offsets.size() == numVariants() + 1) {
+    for (uint32_t i = compact_.offsets[v]; i < compact_.offsets[v + 1]; ++i) {
+      out.push_back(table_.prefixes.at(compact_.prefix[i]));
     }
   } else if (changed_.size() == numVariants() * words_) {
     for (size_t p = 0; p < table_.prefixes.size(); ++p) {

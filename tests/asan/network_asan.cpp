@@ -3,7 +3,9 @@
 // plan building (pair order, the pairs whose source is down), chunk planning
 // at several bounds, the batched / fallback split on a fabric whose FSWs keep
 // two next-hop words and on an area with a zero metric, the validation
-// errors, and the sweep's constructor with its accessors before any launch.
+// errors, and the sweep's constructor with its accessors before any launch;
+// and the pieces the two sweeps share: the counts scan, CompactChanges' chunk
+// order rules, WhatifDeviceLists' upload and descriptor.
 // Exit status 0 = every check passed (the sanitizers abort on a finding).
 #include <algorithm>
 #include <cstdio>
@@ -177,6 +179,96 @@ int main() {
     EXPECT(net.batchedSources() == 3 && net.plan().fallback.size() == 2);
     EXPECT(net.state(1, 0) == NetworkWhatifSweep::kSourceDown);
     EXPECT(net.state(1, 1) == NetworkWhatifSweep::kComputed);
+  }
+  // the counts scan both sweeps share: a refused unit adds nothing
+  {
+    const uint32_t R = OGS_WHATIF_REFUSED;
+    const std::vector<uint32_t> counts = {3, 1, R, R, 0, 2};
+    std::vector<uint32_t> offsets;
+    EXPECT(scanChangeCounts<2>(counts.data(), 3, offsets) == 6);
+    EXPECT(offsets == std::vector<uint32_t>({0, 4, 4, 6}));
+    const std::vector<uint32_t> rows = {2, 0, 5};  // label rows: one count a unit
+    EXPECT(scanChangeCounts<1>(rows.data(), 3, offsets) == 7);
+    EXPECT(offsets == std::vector<uint32_t>({0, 2, 2, 7}));
+    const std::vector<uint32_t> big = {0xFFFFFFFEu, 0, 2, 0};
+    bool threw = false;
+    try {
+      scanChangeCounts<2>(big.data(), 2, offsets);
+    } catch (const std::length_error&) {
+      threw = true;
+    }
+    EXPECT(threw);
+    EXPECT(scanChangeCounts<2>(big.data() + 2, 1, offsets, 0xFFFFFFFDu) == 2);  // 2^32 - 1: fits
+  }
+  // compact records: chunks append in unit order, and only at W = 1 (chunks
+  // without changes reach no device call)
+  {
+    const std::vector<uint32_t> none(8, 0);
+    const ogs_spf_out rec{};
+    auto throwsLogic = [&](CompactChanges& c, size_t u0) {
+      try {
+        c.gather(u0, 2, none.data(), nullptr, rec, 1, nullptr);
+      } catch (const std::logic_error&) {
+        return true;
+      }
+      return false;
+    };
+    CompactChanges one, two;
+    one.reset(4, 1);
+    EXPECT(!throwsLogic(one, 0) && throwsLogic(one, 0) && !throwsLogic(one, 2));
+    EXPECT(throwsLogic(one, 4));  // past the units
+    const ChangeRecords v = one.view();
+    EXPECT(v.variants == 4 && v.total == 0 && v.W == 1 && v.offsets[4] == 0);
+    two.reset(4, 2);
+    EXPECT(!throwsLogic(two, 0) && throwsLogic(two, 2));
+  }
+  // the device scenario lists: no flag list, a revived link among the metrics
+  {
+    Sweep::Scenario down, up, cost;
+    down.linksDown = {{"11", ifn(11, 12)}};
+    LinkState dls(g.area, "test_node");  // the link 12-13 overloaded at one end
+    PrefixState dps;
+    auto dg = topogen::grid(o);
+    for (auto& d : dg.adjDbs) {
+      for (auto& adj : d.adjs) {
+        if (d.thisNodeName == "12" && adj.otherNodeName == "13") adj.isOverloaded = true;
+      }
+    }
+    loadLsdb(dg, dls, dps);
+    up.linksUndrained = {{"12", ifn(12, 13)}};
+    cost.linkMetrics = {{"6", ifn(6, 7), 9}, {"7", ifn(7, 6), 9}};
+    Sweep::Lists lists;
+    for (const Sweep::Scenario* sc : {&down, &up, &cost}) {
+      lists.append(Sweep::expandScenario(dls, "0", *sc));
+    }
+    EXPECT(lists.flagNode.empty() && lists.restores && lists.metricEdge.size() == 4);
+    Sweep::WhatifDeviceLists dl;
+    dl.upload(lists);
+    dl.upload(lists);  // once
+    const ogs_whatif_mods m0 = dl.mods(), m2 = dl.mods(2);
+    EXPECT(!m0.node_off && !m0.node_ids && !m0.node_bits);
+    EXPECT(!m2.node_off && !m2.node_ids && !m2.node_bits);
+    EXPECT(m0.dead_off == dl.deadOff.as<uint32_t>() && m2.dead_off == m0.dead_off + 2);
+    EXPECT(m0.metric_off && m2.metric_off == m0.metric_off + 2);
+    EXPECT(m2.dead_edges == m0.dead_edges && m2.metric_edges == m0.metric_edges &&
+           m2.metric_vals == m0.metric_vals);
+    EXPECT(m0.max_metric_per_unit == lists.maxMetricList && m2.max_metric_per_unit == 2);
+    // (the stub's device memory is host memory)
+    for (size_t i = 0; i < lists.metricEdge.size(); ++i) {
+      EXPECT(m0.metric_edges[i] == lists.metricEdge[i]);
+      EXPECT((m0.metric_vals[i] & ~OGS_WHATIF_EDGE_UP) == uint32_t(lists.metricVal[i]));
+      EXPECT(((m0.metric_vals[i] & OGS_WHATIF_EDGE_UP) != 0) == (lists.metricUp[i] != 0));
+      EXPECT((lists.metricUp[i] != 0) == (i < 2));  // scenario 1 revives, scenario 2 overrides
+    }
+    // no metric list either: only the dead lists are passed
+    Sweep::Lists deadOnly;
+    deadOnly.append(Sweep::expandScenario(dls, "0", down));
+    Sweep::WhatifDeviceLists dd;
+    dd.uploadDead(deadOnly);
+    dd.upload(deadOnly);
+    const ogs_whatif_mods md = dd.mods();
+    EXPECT(md.dead_off && md.dead_edges && !md.node_off && !md.metric_off && !md.metric_vals);
+    EXPECT(md.dead_off[1] == 2 && md.dead_edges[0] == deadOnly.deadList[0]);
   }
   if (failures) {
     std::fprintf(stderr, "network_asan: %d check(s) failed\n", failures);

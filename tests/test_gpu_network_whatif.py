@@ -125,7 +125,7 @@ def test_grid_mix(oracle):
     assert nonempty(answers[me][scs.index({"nodesUndrained": ["12"]})])
 
 
-@pytest.mark.parametrize("chunks", ["default", "small"])
+@pytest.mark.parametrize("chunks", ["default", "small", "unit"])
 def test_grid(product, oracle, chunks):
     w, scs, answers = grid_case(oracle)
     als, ls, ps = w.load(product, "12")
@@ -135,6 +135,13 @@ def test_grid(product, oracle, chunks):
         plan = product.network_whatif_plan(ls, ps, SOURCES, scs)
         net.setChunkBytes(plan["unitBytes"] * (len(plan["pairs"]) // 5))
         assert net.numChunks() >= 4
+    elif chunks == "unit":
+        # one pair a chunk: chunks without a changed route among those with some
+        plan = product.network_whatif_plan(ls, ps, SOURCES, scs)
+        net.setChunkBytes(plan["unitBytes"])
+        assert net.numChunks() == len(plan["pairs"]) >= 3
+        flat = [a for row in answers for a in row if a is not None]
+        assert 0 < sum(nonempty(a) for a in flat) < len(flat)
     else:
         assert net.numChunks() == 1
     net.launch()
